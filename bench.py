@@ -9,10 +9,16 @@ histogram and all-reduces it.  Weak scaling: each rank owns its own slice of glo
 ids; inputs are generated on device from (seed, global id) before the timed region.
 
 Default workload = BASELINE configs[1] (c2): B=4096 per GPU, N=20, fp64, random x0 + hover
-reference.  The line also carries a ``secondary`` measurement of configs[2] (c3: B=65536,
-N=20, fp32, sinusoidal references) at N=1.
+reference.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5]
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds
+what takes runs of its own: the per-phase timing pass and the roofline built on it, the check of
+the launched kernels against the library's plan, a ``secondary`` measurement of configs[2] (c3:
+B=65536, N=20, fp32, sinusoidal references) at N=1, the B=1 latency block and the CPU baseline.
+``--dump-outputs DIR`` writes the outputs of the last timed step as DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--full]
+                    [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -147,7 +153,43 @@ def make_solver(w, B, dev, stub=None):
     return BatchedMPC(cfg, max_batch=B, device=dev)
 
 
-def run(w, world, rank, dev, steps, warmup, stub=None, dump_gather=None):
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, pipe):
+    """``--dump-outputs``: what the last timed step handed back on this rank -- u0 [B,4], X
+    [B,N+1,12], U [B,N,4] and status [B] of the output set it wrote, plus the step's collective
+    result (``histogram`` [4,64] at c5, ``u0_gathered`` [world*B,4] with several ranks) -- one
+    DIR/<name>.npy each, in the solve's own precision (integers as float64).  Above 64 MB in all,
+    the per-instance arrays keep the same seeded sample of instance rows (sorted, seed 0)."""
+    u0, X, U, status = pipe.outs[pipe.last]
+    per_inst = {k: v for k, v in (('u0', u0), ('X', X), ('U', U), ('status', status)) if v is not None}
+    whole = {}
+    if pipe.mode == 'histogram':
+        whole['histogram'] = pipe.result()
+    elif pipe.gathered is not None:
+        whole['u0_gathered'] = pipe.result()
+
+    def nbytes(t):   # as written: float32 stays, everything else becomes float64
+        return t.numel() * (4 if str(t.dtype) == 'torch.float32' else 8)
+    B = u0.shape[0]
+    # 256 bytes per file: room for the .npy header
+    budget = DUMP_MAX_BYTES - sum(nbytes(t) for t in whole.values()) - 256 * (len(per_inst) + len(whole))
+    row_bytes = sum(nbytes(t) for t in per_inst.values()) // B
+    rows = None
+    if B * row_bytes > budget:
+        keep = max(1, budget // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in {**per_inst, **whole}.items():
+        a = t.cpu().numpy()
+        if rows is not None and name in per_inst:
+            a = a[rows]
+        np.save(os.path.join(dirname, name + '.npy'),
+                np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+
+
+def run(w, world, rank, dev, steps, warmup, stub=None, dump_gather=None, full=False, dump_dir=None):
     import torch
     import torch.distributed as dist
 
@@ -201,16 +243,20 @@ def run(w, world, rank, dev, steps, warmup, stub=None, dump_gather=None):
     bad = pipe.bad_status()
     if dump_gather and rank == 0:   # the gathered u0 [world*B, 4] (or histogram) of the last step
         np.save(dump_gather, pipe.result().cpu().numpy())
-    # per-phase device time (HIP events the library records on the launch stream around each
-    # kernel); a separate pass so that reading the events does not serialise the timed region
-    mpc.set_timing(True)
-    phases = []
-    for _ in range(steps):
-        step()
-        phases.append(mpc.last_timing())
-    drain()
-    mpc.set_timing(False)
-    phase_ms = {k: float(np.mean([p[k] for p in phases])) for k in phases[0]}
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, pipe)
+    phase_ms = None
+    if full:
+        # per-phase device time (HIP events the library records on the launch stream around each
+        # kernel); a separate pass so that reading the events does not serialise the timed region
+        mpc.set_timing(True)
+        phases = []
+        for _ in range(steps):
+            step()
+            phases.append(mpc.last_timing())
+        drain()
+        mpc.set_timing(False)
+        phase_ms = {k: float(np.mean([p[k] for p in phases])) for k in phases[0]}
     if world > 1:
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=odev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -218,11 +264,12 @@ def run(w, world, rank, dev, steps, warmup, stub=None, dump_gather=None):
         bb = torch.tensor([bad], dtype=torch.int64, device=odev)
         dist.all_reduce(bb)
         bad = int(bb.item())
-        ph = torch.tensor([phase_ms[k] for k in sorted(phase_ms)], dtype=torch.float64, device=odev)
-        dist.all_reduce(ph, op=dist.ReduceOp.MAX)
-        phase_ms = dict(zip(sorted(phase_ms), ph.tolist()))
+        if full:
+            ph = torch.tensor([phase_ms[k] for k in sorted(phase_ms)], dtype=torch.float64, device=odev)
+            dist.all_reduce(ph, op=dist.ReduceOp.MAX)
+            phase_ms = dict(zip(sorted(phase_ms), ph.tolist()))
     qp = None
-    if w['box']:   # active-set work of the last solve: forward passes, masked backward stages
+    if full and w['box']:   # active-set work of the last solve: forward passes, masked backward stages
         st = mpc.qp_stats(B).double().cpu().numpy()
         qp = dict(fwd_passes=float(st[:, 0].sum()), bwd_stages=float(st[:, 1].sum()),
                   mean_iters=float(st[:, 0].mean()), max_iters=int(st[:, 0].max()))
@@ -241,7 +288,7 @@ def run(w, world, rank, dev, steps, warmup, stub=None, dump_gather=None):
     # against the device-free plan of the same config (mpcb_plan_kernels) that the CPU tests pin
     # to the committed PMC summaries
     kernels = mpc.last_kernels()
-    if cuda:
+    if cuda and full:
         plan = mpc.plan_kernels(B, want_traj=traj)
         if plan != kernels:
             raise SystemExit(f'launched kernels {kernels} differ from the plan {plan}')
@@ -429,9 +476,18 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', default='c2', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None, help='override the per-GPU batch')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true')
-    ap.add_argument('--no-latency', action='store_true', help='skip the B=1 per-step latency block')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: per-phase times and the roofline, '
+                         'the launched kernels checked against the plan, the secondary workload, '
+                         'the B=1 latency block and the CPU baseline (each with its --no-* switch)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write the last step\'s outputs (u0, X, U, status; '
+                         'histogram at c5) as DIR/<name>.npy, float32 or float64, at most 64 MB in '
+                         'all (a fixed seeded sample of instances above that)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary workload')
+    ap.add_argument('--no-latency', action='store_true',
+                    help='with --full: skip the B=1 per-step latency block')
     ap.add_argument('--cpu-budget', type=float, default=12.0)
     ap.add_argument('--max-as-iter', type=int, default=200, help='active-set cap (box workload)')
     ap.add_argument('--secondary-batch', type=int, default=None,
@@ -487,18 +543,18 @@ def main():
             dist.init_process_group('gloo', timeout=tmo)
 
     r = run(w, world, rank, dev, args.steps, args.warmup, stub=args.solver_stub,
-            dump_gather=args.dump_gather)
+            dump_gather=args.dump_gather, full=args.full, dump_dir=args.dump_outputs)
     # the secondary line: the BASELINE config quoted at this GPU count, so that the driver's
     # 1/4/8-GPU runs each time the config named for that count -- c3 (configs[2], 1 GPU), c4
     # (configs[3]: 262144 instances sharded over 4 GPUs, input box) and c5 (configs[4]: 1048576
     # over 8 GPUs, RCCL all_reduce of the u0* histogram)
     sec = None
     sec_name = {1: 'c3', 4: 'c4', 8: 'c5'}.get(world)
-    if sec_name and args.workload == 'c2' and not args.no_secondary and (cuda or world > 1):
+    if args.full and sec_name and args.workload == 'c2' and not args.no_secondary and (cuda or world > 1):
         ws = dict(WORKLOADS[sec_name], name=sec_name, max_as_iter=args.max_as_iter)
         if args.secondary_batch:
             ws['batch'] = args.secondary_batch
-        rs = run(ws, world, rank, dev, args.steps, args.warmup, stub=args.solver_stub,
+        rs = run(ws, world, rank, dev, args.steps, args.warmup, stub=args.solver_stub, full=True,
                  dump_gather=(args.dump_gather + '.secondary.npy') if args.dump_gather else None)
         if rank == 0:
             vs, roofs = summarize(ws, rs, world, args.steps)
@@ -513,8 +569,11 @@ def main():
 
     if rank == 0:
         coll = 'RCCL' if args.backend == 'nccl' else 'gloo'
-        value, roof = summarize(w, r, world, args.steps)
         B, N = w['batch'], w['N']
+        if args.full:
+            value, roof = summarize(w, r, world, args.steps)
+        else:
+            value, roof = B * world * args.steps / r['elapsed'], None
         line = {
             'metric': 'MPC solves/sec (N=%d, nx=12, nu=4)' % N,
             'value': value,
@@ -539,14 +598,16 @@ def main():
             'roofline': roof,
             'bad_status': r['bad'],
         }
+        if roof is None:
+            del line['roofline']
         if not cuda:
             line['data'] += f'; CPU solver stub {args.solver_stub} over {args.backend} (launcher test)'
         if sec is not None:
             line['secondary'] = sec
-        if world == 1 and cuda and args.workload == 'c2' and not args.no_latency:
+        if args.full and world == 1 and cuda and args.workload == 'c2' and not args.no_latency:
             from mpc_blaster_amd.latency import measure_b1
             line['latency_b1'] = measure_b1(device=dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line['cpu_baseline'] = cpu_baseline(w, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -61,13 +61,89 @@ def test_bench_gpus_1_runs_in_process(tmp_path):
     assert got.shape == (8, 4)
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line is the headline alone (no roofline, secondary, latency or CPU
+    baseline blocks), --steps is the number of timed steps, and --dump-outputs writes what the last
+    timed step returned: u0, X, U and status of every instance, equal to the oracle's solve."""
+    from oracle.inputs import make_inputs
+    from oracle.ocp import OcpSpec, mpc_solve
+    d = tmp_path / 'outs'
+    line, _ = _run_bench(tmp_path, 'c2', 1, 6, steps=3, extra=['--dump-outputs', str(d)])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in line
+    for k in ('roofline', 'secondary', 'latency_b1', 'cpu_baseline'):
+        assert k not in line
+    assert line['steps'] == 3
+    assert line['value'] == pytest.approx(6 * 1e3 / line['ms_per_step'], rel=1e-9)
+    assert sorted(p.name for p in d.iterdir()) == ['U.npy', 'X.npy', 'status.npy', 'u0.npy']
+    inp = make_inputs('c2', ids=np.arange(6, dtype=np.uint64), N=20)
+    ref = mpc_solve(inp['x0'], inp['xref'], inp['uref'], OcpSpec(N=20))
+    for name, shape in (('u0', (6, 4)), ('X', (6, 21, 12)), ('U', (6, 20, 4))):
+        got = np.load(str(d / f'{name}.npy'))
+        assert got.dtype == np.float64 and got.shape == shape
+        assert np.array_equal(got, ref[name])
+    st = np.load(str(d / 'status.npy'))
+    assert st.dtype == np.float64 and np.array_equal(st, np.zeros(6))
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path):
+    """Above 64 MB the per-instance arrays keep one seeded sample of rows, the same in every run."""
+    import torch
+    import bench
+
+    class Pipe:
+        mode, gathered, last = 'gather', None, 0
+        outs = [(torch.arange(40.0, dtype=torch.float32).reshape(10, 4), None, None,
+                 torch.zeros(10, dtype=torch.int32))]
+    old = bench.DUMP_MAX_BYTES
+    # room for 5 of the 10 rows (u0 fp32, status as fp64) and the two files' .npy headers
+    bench.DUMP_MAX_BYTES = 5 * (4 * 4 + 8) + 2 * 256
+    try:
+        bench.dump_outputs(str(tmp_path / 'a'), Pipe)
+        bench.dump_outputs(str(tmp_path / 'b'), Pipe)
+        assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) <= bench.DUMP_MAX_BYTES
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    a, b = np.load(str(tmp_path / 'a' / 'u0.npy')), np.load(str(tmp_path / 'b' / 'u0.npy'))
+    assert a.dtype == np.float32 and a.shape == (5, 4) and np.array_equal(a, b)
+    rows = (a[:, 0] / 4).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, Pipe.outs[0][0].numpy()[rows])
+    assert np.load(str(tmp_path / 'a' / 'status.npy')).shape == (5,)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_on_the_gpu(tmp_path):
+    """The HIP path's plain run: two runs with the same arguments dump identical arrays, and they
+    match the fp64 oracle on the same seeded instances (the bound of smoke(): 1e-9 relative)."""
+    from oracle.inputs import make_inputs
+    from oracle.ocp import OcpSpec, mpc_solve
+    outs = []
+    for tag in ('a', 'b'):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+               '--batch', '96', '--dump-outputs', str(d)]
+        p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stderr[-4000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 2 and line['bad_status'] == 0 and 'roofline' not in line
+        outs.append({n: np.load(str(d / f'{n}.npy')) for n in ('u0', 'X', 'U', 'status')})
+    inp = make_inputs('c2', ids=np.arange(96, dtype=np.uint64), N=20)
+    ref = mpc_solve(inp['x0'], inp['xref'], inp['uref'], OcpSpec(N=20))
+    for n in ('u0', 'X', 'U'):
+        assert outs[0][n].dtype == np.float64
+        assert np.array_equal(outs[0][n], outs[1][n])
+        err = np.abs(outs[0][n] - ref[n]).max() / max(np.abs(ref[n]).max(), 1.0)
+        assert err < 1e-9, (n, err)
+    assert not outs[0]['status'].any()
+
+
 def test_bench_gpus_4_adds_the_c4_secondary(tmp_path):
     """At 4 ranks the line also times BASELINE configs[3] (c4: input box, instance-sharded over 4
     GPUs); the gathered c4 u0 equals the unsharded oracle's active-set solution."""
     from oracle.inputs import make_inputs
     from oracle.ocp import OcpSpec, mpc_solve
     sb = 3
-    line, _ = _run_bench(tmp_path, 'c2', 4, 4, steps=1, extra=['--secondary-batch', str(sb)])
+    line, _ = _run_bench(tmp_path, 'c2', 4, 4, steps=1, extra=['--full', '--secondary-batch', str(sb)])
     assert line['n_gpus'] == 4 and line['config']['global_batch'] == 16
     sec = line['secondary']
     assert sec['workload'].startswith('c4') and sec['global_batch'] == 4 * sb and sec['n_gpus'] == 4
@@ -88,7 +164,7 @@ def test_bench_gpus_8_adds_the_c5_histogram_secondary(tmp_path):
     from oracle.inputs import make_inputs
     from oracle.ocp import OcpSpec, mpc_solve
     sb = 3
-    line, _ = _run_bench(tmp_path, 'c2', 8, 2, steps=1, extra=['--secondary-batch', str(sb)])
+    line, _ = _run_bench(tmp_path, 'c2', 8, 2, steps=1, extra=['--full', '--secondary-batch', str(sb)])
     assert line['n_gpus'] == 8 and line['config']['global_batch'] == 16
     sec = line['secondary']
     assert sec['workload'].startswith('c5') and sec['global_batch'] == 8 * sb and sec['n_gpus'] == 8

@@ -13,7 +13,7 @@ IFS=';' read -ra CS <<< "$CASES"
 for rep in a b; do
   for c in "${CS[@]}"; do
     name=${c%%=*}; envs=${c#*=}
-    env $envs timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --no-latency --workload $W --steps 50 --warmup 20 > $O/${W}${rep}_$name.log 2>&1
+    env $envs timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-secondary --no-latency --workload $W --steps 50 --warmup 20 > $O/${W}${rep}_$name.log 2>&1
     python3 -c "import json,sys; d=json.loads(open('$O/${W}${rep}_$name.log').read().strip().splitlines()[-1]); print('$rep $name', round(d['ms_per_step'],4), {k: round(x,4) for k,x in d['roofline']['phase_ms'].items()})"
   done
 done

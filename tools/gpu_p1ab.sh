@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 bash tools/var_phases.sh ${1:-p1ab}/c2 "${2:-noown}" c2
 if [ -n "$3" ]; then   # then the c2 bench line and its profiles
-  timeout -k 10 300 python bench.py > $O/bench_default.log 2>&1
+  timeout -k 10 300 python bench.py --full > $O/bench_default.log 2>&1
   WORKLOADS=c2 bash tools/collect_profiles.sh ${1:-p1ab}
 fi
 echo p1ab_done

@@ -12,11 +12,11 @@ PART=${PART:-all}
 if [ "$PART" != 2 ]; then
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $O/gpu_tests.log 2>&1
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-timeout -k 10 300 python bench.py > $O/bench_default.log 2>&1
+timeout -k 10 300 python bench.py --full > $O/bench_default.log 2>&1
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_torchrun.log 2>&1
+  --master-port 29517 bench.py --full --gpus 1 --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_torchrun.log 2>&1
 for w in c3 c4 c5; do
-  timeout -k 10 300 python bench.py --workload $w --cpu-budget 6 > $O/bench_$w.log 2>&1
+  timeout -k 10 300 python bench.py --full --workload $w --cpu-budget 6 > $O/bench_$w.log 2>&1
 done
 bash tools/collect_profiles.sh ${1:-round_end}
 fi

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
-"""Print value / per-phase ms of gpurun_out/var_*.log (tools/var_bench.sh output)."""
+"""Print value / per-phase ms of DIR/var_*.log (tools/var_bench.sh output; DIR = argv[1], default
+$VAR_OUT or var_out)."""
 import glob
 import json
 import os
+import sys
 
-for f in sorted(glob.glob('gpurun_out/var_*.log'), key=os.path.getmtime):
+DIR = sys.argv[1] if len(sys.argv) > 1 else os.environ.get('VAR_OUT', 'var_out')
+for f in sorted(glob.glob(os.path.join(DIR, 'var_*.log')), key=os.path.getmtime):
     for line in open(f):
         if line.startswith('{'):
             d = json.loads(line)
