@@ -135,6 +135,16 @@ static void fill_weights(const mpcb_config& c, Weights<T>& w) {
     w.ctab[d * ABT2_W + sl] = T(1);
     if (d >= 6) w.ctab[(d - 6) * ABT2_W + sl] = hv;
   }
+  // the Riccati prologue's lane-ordered tables; s * (wq + wr) as the kernels form it
+  const T s = (T)c.cost_scale;
+  for (int j = 0; j < NZ; ++j)
+    for (int i = 0; i < NZ; ++i) {
+      const T wq = (i < NX && j < NX) ? w.Q[i * NX + j] : T(0);
+      const T wr = (i >= NX && j >= NX) ? w.R[(i - NX) * NU + (j - NX)] : T(0);
+      w.swt[j * NZ + i] = s * (wq + wr);
+    }
+  for (int j = 0; j < NZ; ++j)
+    for (int i = 0; i < NX; ++i) w.qnc[j * NX + i] = j < NX ? w.QN[i * NX + j] : T(0);
 }
 
 template <class T>

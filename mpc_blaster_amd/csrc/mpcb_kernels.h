@@ -24,6 +24,12 @@ struct Weights {
   // (h/6)*6) laid out like an ABT2 record -- entry i of slot s at i * 10 + s -- so a lane of a
   // constant direction reads its column with the variable lanes' strided loads (mpcb_as.hip)
   T ctab[NX * 10];
+  // lane-ordered tables of the fp64 Riccati prologue (riccati_body, the tangent-reading path), so
+  // lane j reads what it keeps for the whole recursion with 16-byte loads instead of gathering it
+  // through LDS: swt[j * NZ + i] = s * blkdiag(Q, R)[i][j] (s = the stage cost scale) and
+  // qnc[j * NX + i] = QN[i][j] (zero for the input lanes j >= NX)
+  alignas(16) T swt[NZ * NZ];
+  alignas(16) T qnc[NZ * NX];
 };
 
 template <class T>
@@ -74,7 +80,7 @@ inline bool dry_run() { return launch_log().dry; }
   } while (0)
 enum { PH_NOMINAL = 0, PH_RICCATI = 1, PH_FORWARD = 2, PH_LIN17 = 2, PH_LIN = 3 };
 // Static LDS of the fp64 Riccati body (riccati_body: GroupLds x 4, SW, Cst), the same in
-// row_riccati_kernel and riccati_kernel_f64 (tools/kernel_meta.py: 24064 B); mpcb_create sizes
+// row_riccati_kernel and riccati_kernel_f64 (tools/kernel_meta.py: at most 24064 B); mpcb_create sizes
 // the fused launch with it and launch_split checks it against the code object before the first
 // fused launch (the solve fails loudly if it grew).
 constexpr size_t RICCATI_F64_STATIC_LDS = 24064;

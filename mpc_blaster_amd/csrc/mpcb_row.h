@@ -267,11 +267,18 @@ __device__ __forceinline__ void row_body(const SplitArgs<T>& a) {
   const T* const lxq = lx + q * (N + 1) * NX;
   const T* const luq = lu + q * N * NU;
   if (ITER && t < NX) X = lxq[t];
+  // the input lanes' u_k is read from LDS one interval ahead (every lane reads, the state lanes
+  // an unused copy), so neither its latency nor a lane branch sits at the interval's start
+  const T* const lul = luq + (t >= NX ? t - NX : 0);
+  T Un = N > 0 ? lul[0] : T(0);
+  // the lane's ABT2 export slot of interval k, stepped by a constant
+  T* abt = TAN ? rec2(a.ABT, 0, ABT2_REC, nb, c, N, a.imajor) + (tv >= 0 ? tv : 0) : nullptr;
+  const int64_t abt_k = (a.imajor ? 1 : nq * SS) * (int64_t)ABT2_REC;
 
   WT(g_wt_p1, 1);
   for (int k = 0; k < N; ++k) {
     if (ITER && t < NX && k) X = lxq[k * NX + t];
-    if (t >= NX) X = luq[k * NU + (t - NX)];
+    if (t >= NX) X = Un;
     xu0[k * xu_k + t * SS] = X;
     // per-interval constants: the inputs, the thrust scale and J^-1 M(u) + the constant forces
     const T u0 = rbc<12>(X), u1 = rbc<13>(X), u2 = rbc<14>(X), u3 = rbc<15>(X);
@@ -429,11 +436,14 @@ __device__ __forceinline__ void row_body(const SplitArgs<T>& a) {
       // column var_col(tv) of [A_k | B_k] into the ABT2 rows: entry (i, tv) at i * ABT2_W + tv.
       // (Staging the wave's four records in LDS and writing them as 16-B vectors measured the
       // same P1 time, 50.3 us at c2, with 75 more instructions per interval.)
+      Un = lul[(k + 1 < N ? k + 1 : k) * NU];
       if (exp_lane) {
-        T* const abt = rec2(a.ABT, k, ABT2_REC, nb, c, N, a.imajor) + tv;
 #pragma unroll
         for (int i = 0; i < NX; ++i) abt[i * ABT2_W] = dN[i];
       }
+      abt += abt_k;
+    } else {
+      Un = lul[(k + 1 < N ? k + 1 : k) * NU];
     }
     if (ITER) {
       if (t < NX) gp0[k * gp_k + t * SS] = Xn - lxq[(k + 1) * NX + t];

@@ -488,6 +488,9 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   // so u0 would differ in the last bit between want_traj = 0 and 1 (test_u0_only_path_equals_full_path)
   constexpr bool R32 = sizeof(T) == 4 && EXPORT && MPCB_P2_R32;
   constexpr bool DREG = D64 || R32;
+  // DT (fp64 DPP path reading the rollout's tangents): the prologue's handle constants come from
+  // the lane-ordered tables of Weights, and column j of [A|B] is loaded where it is consumed
+  constexpr bool DT = D64 && TIN;
   __shared__ GroupLds<T> lds_all[GROUPS];
   const int lane = threadIdx.x;
   const int q = lane >> 4;
@@ -520,15 +523,69 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   // s * blkdiag(Q, R) in LDS: lane j reads column j (= row j), so the stage-cost terms are the
   // same instruction stream in state and input lanes (no divergent branch per stage)
   __shared__ __attribute__((aligned(16))) T SW[NZ * NZ];
-  for (int e = lane; e < NZ * NZ; e += 64) {
-    const int r = e / NZ, cl = e % NZ;
-    const T wq = (r < NX && cl < NX) ? W.Q[r * NX + cl] : T(0);
-    const T wr = (r >= NX && cl >= NX) ? W.R[(r - NX) * NU + (cl - NX)] : T(0);
-    SW[e] = s * (wq + wr);
+  if constexpr (!DT) {
+    for (int e = lane; e < NZ * NZ; e += 64) {
+      const int r = e / NZ, cl = e % NZ;
+      const T wq = (r < NX && cl < NX) ? W.Q[r * NX + cl] : T(0);
+      const T wr = (r >= NX && cl >= NX) ? W.R[(r - NX) * NU + (cl - NX)] : T(0);
+      SW[e] = s * (wq + wr);
+    }
   }
   T pj;      // p_{k+1}[j]
   T Pc[NX];  // column j of P_{k+1} (zero in the input lanes: P padded to 16x16)
-  {
+  T sw[NZ];  // DREG: column j of s blkdiag(Q, R)
+  // DT: the stage data of lane j is loaded one stage ahead through running pointers, stepped by a
+  // constant per stage: column j of [A|B] from the ABT2 rows (variable directions) or from
+  // Weights::ctab (the constant ones, step 0), the own component of (xbar | ubar) and of the
+  // reference, and (iterate mode) of the gap
+  T col[NX], cyb, cyr, pgp = T(0);
+  const int tvj = var_index(j);
+  const int64_t nq4 = (nb + SS - 1) / SS;
+  const int64_t rstep = a.imajor ? 1 : nq4 * SS;   // rec2 records per stage
+  const T* pcol = nullptr; const T* pxu = nullptr; const T* pref = nullptr; const T* pgpp = nullptr;
+  T* pkr = nullptr;
+  int64_t scol = 0, sref = 0;
+  auto load_stage = [&]() {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) col[i] = pcol[i * ABT2_W];
+    cyb = *pxu;
+    cyr = *pref;
+    if (iterate) pgp = *pgpp;
+    pcol -= scol;
+    pxu -= nq4 * (XU_REC * SS);
+    pref -= sref;
+    if (iterate) pgpp -= nq4 * (GP_REC * SS);
+  };
+  if constexpr (DT) {
+    // every load of the prologue is issued before its first wait: the terminal state and
+    // reference, the lane's table rows and the last stage's data
+    const T xN = soa(a.XU, N, XU_REC, nb, c)[jx * SS];
+    const T xrN = xr[(int64_t)N * NX + jx];
+    T qr[NX];
+    ldv<T, NX>(W.QN + jx * NX, qr);
+    ldv<T, NX>(W.qnc + j * NX, Pc);
+    ldv<T, NZ>(W.swt + j * NZ, sw);
+    if (N > 0) {
+      const int cslot = j < 3 ? j : j - 3;   // (constant directions 0..2, 6..8)
+      pcol = tvj >= 0 ? rec2(a.ABT, N - 1, ABT2_REC, nb, c, N, a.imajor) + tvj : W.ctab + cslot;
+      scol = tvj >= 0 ? rstep * ABT2_REC : 0;
+      pxu = soa(a.XU, N - 1, XU_REC, nb, c) + j * SS;
+      pref = (j < NX) ? xr + (int64_t)(N - 1) * NX + jx : ur + (int64_t)(N - 1) * NU + ju;
+      sref = j < NX ? NX : NU;
+      if (iterate) pgpp = soa(a.GP, N - 1, GP_REC, nb, c) + jx * SS;
+      pkr = rec2(a.KR, N - 1, KR2_REC, nb, c, N, a.imajor) + (j <= NX ? j : NX + 1);
+      load_stage();
+    }
+#pragma unroll
+    for (int i = 0; i < NZ; ++i) asm volatile("" : "+v"(sw[i]));
+    L.v[j] = (j < NX) ? xN - xrN : T(0);
+    wave_lds_sync();
+    T acc = T(0);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) acc += qr[i] * L.v[i];
+    pj = acc;
+    wave_lds_sync();
+  } else {
     const T xN = soa(a.XU, N, XU_REC, nb, c)[jx * SS];
     L.v[j] = (j < NX) ? xN - xr[(int64_t)N * NX + jx] : T(0);
     wave_lds_sync();
@@ -546,6 +603,7 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   }
   bool qp_ok = true;
   T kff0 = T(0);
+  T kffl[NU] = {T(0), T(0), T(0), T(0)};   // DT: the last stage's k
   // Stage data is prefetched one stage ahead into registers (5 linearisation scalars, the own
   // component of ybar and yref, one gap value per lane) and committed to a double-buffered LDS
   // copy, so the tangent integrates from LDS and no global-load latency sits on the chain.
@@ -553,8 +611,7 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   // group stride padded so that two groups' broadcast reads of the same scalar fall on different
   // banks (96 elements put them on one bank: a 2-way conflict on every tangent read)
   __shared__ T Cst[2][GROUPS][CCS_REC + NZ + MPCB_P2_CPAD];
-  T pc[TIN ? NX : 5], pyb, pyr, pgp = T(0);
-  const int tvj = var_index(j);
+  T pc[TIN ? NX : 5], pyb, pyr;
   const T kvar = T(tvj >= 0);   // TIN: 1 on the variable directions, 0 on the constant ones
   T ce[NX];                     // TIN: the constant column (0 on the variable directions)
 #pragma unroll
@@ -586,8 +643,7 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   };
   // D64: s blkdiag(Q, R) column j (the G accumulators' initial values) in registers for the
   // whole recursion: 16 LDS reads and their waits less per stage
-  T sw[NZ];
-  if constexpr (DREG) {
+  if constexpr (DREG && !DT) {
     wave_lds_sync();
 #pragma unroll
     for (int i = 0; i < NZ; ++i) {
@@ -595,21 +651,24 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
       asm volatile("" : "+v"(sw[i]));
     }
   }
-  prefetch(N - 1);
-  commit(0);
-  T cyb = pyb, cyr = pyr;
+  if constexpr (!DT) {
+    prefetch(N - 1);
+    cyb = pyb; cyr = pyr;
+  }
+  if (!DT || iterate) commit(0);
   int buf = 0;
   wave_lds_sync();
   STAMP_INIT();
   WT(g_wt_p2, 1);
   for (int k = N - 1; k >= 0; --k) {
-    T col[NX];
     T ptr = T(0);   // R32: this lane's entry of p + P gap
-    if constexpr (TIN) {
+    if constexpr (TIN && !DT) {
 #pragma unroll
       for (int i = 0; i < NX; ++i) col[i] = fma(kvar, pc[i], ce[i]);
     }
-    if (k > 0) prefetch(k - 1);
+    if constexpr (!DT) {
+      if (k > 0) prefetch(k - 1);
+    }
     STAMP(0);
     {
       const T* cc = &Cst[buf][q][0];
@@ -685,6 +744,11 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
 #endif
 #pragma unroll
       for (int i = 0; i < NZ; ++i) G[i] = g[i];
+      if constexpr (DT) {
+        // the stage's column, state and reference are consumed: the next stage's land in their
+        // place behind the factorisation, the gains and the P update (one wait at the first use)
+        if (k > 0) load_stage();
+      }
     } else if constexpr (R32) {
       // h = [A|B]^T pt with pt_l broadcast from lane l, plus the stage cost's (S v)_j
       T acc4[4] = {T(0), T(0), T(0), T(0)};
@@ -792,8 +856,22 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
       }
     }
     STAMP(6);
-    kff0 = sel<NU>(kff, ju);
-    if (D64 && (TIN || a.rm)) {
+    if constexpr (DT) {
+      // KR2 through the running pointer (it carries the lane's slot): four stores from every lane
+      // and no lane branch (below).  State lane j writes K[m][j]; every lane holds the whole of
+      // k (the input block is factorised redundantly), so input lane 12 writes k_m to slot 12 of
+      // every row and the other input lanes write theirs to the rows' pad slot 13.
+#pragma unroll
+      for (int m = 0; m < NU; ++m) {
+        pkr[m * KR2_W] = (j < NX) ? Kj[m] : kff[m];
+        kffl[m] = kff[m];
+      }
+      pkr -= rstep * KR2_REC;
+    } else {
+      kff0 = sel<NU>(kff, ju);
+    }
+    if constexpr (DT) {
+    } else if (D64 && (TIN || a.rm)) {
       // KR2 (TIN: always this layout), four stores from every lane and no lane branch, so the
       // next stage's wait for its prefetched loads counts exactly these stores (a path without
       // them made the compiler wait for every store to complete, vmcnt(0)): state lane j writes
@@ -833,9 +911,10 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
       for (int i = 0; i < NX; ++i) L.X[j * XS + i] = Pn[i];
     }
     pj = pn;
-    if (k > 0) commit(buf ^ 1);
+    // (DT, rollout mode: the gap slot of Cst is never read)
+    if ((!DT || iterate) && k > 0) commit(buf ^ 1);
     wave_lds_sync();
-    if (EXPORT && a.PS && valid && j < NX && k > 0) {
+    if (publish && EXPORT && a.PS && valid && j < NX && k > 0) {
       // box path: the value function P_k, p_k packed by symmetry (mpcb_kernels.h PS2), so the
       // active-set kernel's first masked pass restarts above the highest violated stage instead
       // of recomputing the whole horizon; slot d of lane j is P[j][(j + d) % 12], published by
@@ -875,12 +954,15 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
       }
     }
     buf ^= 1;
-    cyb = pyb;
-    cyr = pyr;
+    if constexpr (!DT) {
+      cyb = pyb;
+      cyr = pyr;
+    }
     STAMP(9);
   }
   STAMP_DONE();
   WT(g_wt_p2, 2);
+  if constexpr (DT) kff0 = sel<NU>(kffl, ju);
   if (valid && j == NX) a.status[b] = qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL;
   if (valid && !a.fwd && j >= NX) {
     // rollout mode without trajectories: dx_0 = 0 so u0 = ubar_0 + kff_0
