@@ -147,6 +147,62 @@ static void fill_weights(const mpcb_config& c, Weights<T>& w) {
     for (int i = 0; i < NX; ++i) w.qnc[j * NX + i] = j < NX ? w.QN[i * NX + j] : T(0);
 }
 
+// Weights::rowt: the lane constants of the row rollout (mpcb_row.h row_body), with the arithmetic
+// the kernel used when it built them per wave.  The device contracts `g += a * b` into one fma,
+// so every multiply-add here is an explicit fma and every other operation a lone IEEE add or
+// multiply: the table holds the bits the kernel computed.
+template <class T>
+static void fill_row_table(const Model<T>& M, T* rowt) {
+  auto Jm = [&](int m, int l) { return M.J[m * 3 + l]; };
+  // (w x Jw)_i = sum_jl B_i[j][l] w_j w_l with B_i[j][l] = sum_m eps_ijm J_ml, over the products
+  // p = (w0 w0, w1 w1, w2 w2, w0 w1, w0 w2, w1 w2)
+  T coef[3][6];
+  for (int i = 0; i < 3; ++i) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;   // eps_{i,i1,i2} = +1, eps_{i,i2,i1} = -1
+    auto B = [&](int j, int l) {
+      return (j == i1 ? Jm(i2, l) : T(0)) - (j == i2 ? Jm(i1, l) : T(0));
+    };
+    coef[i][0] = B(0, 0); coef[i][1] = B(1, 1); coef[i][2] = B(2, 2);
+    coef[i][3] = B(0, 1) + B(1, 0); coef[i][4] = B(0, 2) + B(2, 0); coef[i][5] = B(1, 2) + B(2, 1);
+  }
+  // mixer (blastermodel.py:95-101): M = [ly(u1+u3-u0-u2), lx(u1+u2-u0-u3), c(u2+u3-u0-u1)]
+  const T mix[3][4] = {{-M.ly, M.ly, -M.ly, M.ly}, {-M.lx, M.lx, M.lx, -M.lx}, {-M.c, -M.c, M.c, M.c}};
+  for (int t = 0; t < NZ; ++t) {
+    T* const o = rowt + t * ROW_TAB_W;
+    for (int i = 0; i < ROW_TAB_W; ++i) o[i] = T(0);
+    o[ROWT_GRAV] = t == 8 ? M.g : T(0);
+    const int r = (t >= 9 && t < 12) ? t - 9 : -1;
+    auto Jir = [&](int i) { return r >= 0 ? M.Jinv[r * 3 + i] : T(0); };
+    // G_t,p = -sum_i Jinv[t-9][i] coef_i,p;  Lm: f_t's constant part is sum_m Lm[m] u_m
+    for (int p = 0; p < 6; ++p) {
+      T g = T(0);
+      for (int i = 0; i < 3; ++i) g = std::fma(Jir(i), coef[i][p], g);
+      o[p < 3 ? ROWT_G0 + p : ROWT_G3 + p - 3] = -g;
+    }
+    for (int m = 0; m < 4; ++m) {
+      T l = T(0);
+      for (int i = 0; i < 3; ++i) l = std::fma(Jir(i), mix[i][m], l);
+      o[ROWT_LM + m] = l;
+    }
+    const int jr = r >= 0 ? r : 0;
+    for (int l = 0; l < 3; ++l) o[ROWT_J + l] = M.J[jr * 3 + l];
+    // the tangent of direction e_t: its input part e_{t-12} on lanes 12..15
+    const int m = t >= NX ? t - NX : -1;
+    o[ROWT_DSL] = m >= 0 ? M.minv : T(0);
+    const T mixm[3] = {m < 0 ? T(0) : ((m == 1 || m == 3) ? M.ly : -M.ly),
+                       m < 0 ? T(0) : ((m == 1 || m == 2) ? M.lx : -M.lx),
+                       m < 0 ? T(0) : ((m == 2 || m == 3) ? M.c : -M.c)};
+    for (int i = 0; i < 3; ++i) {
+      const T last = M.Jinv[i * 3 + 2] * mixm[2];
+      o[ROWT_JU + i] = std::fma(M.Jinv[i * 3], mixm[0], std::fma(M.Jinv[i * 3 + 1], mixm[1], last));
+    }
+    const T d0 = M.J[8] - M.J[4], d1 = M.J[0] - M.J[8], d2 = M.J[4] - M.J[0];
+    o[ROWT_KD] = -M.Jinv[0] * d0;
+    o[ROWT_KD + 1] = -M.Jinv[4] * d1;
+    o[ROWT_KD + 2] = -M.Jinv[8] * d2;
+  }
+}
+
 template <class T>
 static void fill_weights17(const mpcb_config& c, Weights17<T>& w) {
   for (int i = 0; i < NX17 * NX17; ++i) {
@@ -208,6 +264,27 @@ static int validate_config(const mpcb_config* cfg, int64_t max_batch, double Jin
   if (max_batch < 1) return fail(MPCB_E_INVALID, "max_batch=%lld", (long long)max_batch);
   if (cfg->box_u && cfg->max_as_iter < 1) return fail(MPCB_E_INVALID, "max_as_iter must be >= 1");
   if (!inv3(cfg->J, Jinv)) return fail(MPCB_E_INVALID, "inertia J is singular");
+  return MPCB_OK;
+}
+
+// The row table of a config as doubles (NZ * ROW_TAB_W values, lane-major), without a device:
+// what mpcb_create uploads in Weights::rowt (tests/test_row_table.py).
+extern "C" int mpcb_debug_row_table(const mpcb_config* cfg, double* out) {
+  if (!cfg || !out) return fail(MPCB_E_INVALID, "null argument");
+  double Jinv[9];
+  if (int rc = validate_config(cfg, 1, Jinv)) return rc;
+  if (cfg->nx != NX) return fail(MPCB_E_UNSUPPORTED, "the row table belongs to the 12/4 model");
+  if (cfg->dtype == MPCB_F64) {
+    Model<double> M;
+    fill_model(*cfg, Jinv, M);
+    fill_row_table(M, out);
+  } else {
+    Model<float> M;
+    float tab[NZ * ROW_TAB_W];
+    fill_model(*cfg, Jinv, M);
+    fill_row_table(M, tab);
+    for (int i = 0; i < NZ * ROW_TAB_W; ++i) out[i] = tab[i];
+  }
   return MPCB_OK;
 }
 
@@ -348,10 +425,12 @@ extern "C" int mpcb_create(const mpcb_config* cfg, int device, int64_t max_batch
   } else if (f64) {
     Weights<double> w;
     fill_weights(*cfg, w);
+    fill_row_table(h->Md, w.rowt);
     e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
   } else {
     Weights<float> w;
     fill_weights(*cfg, w);
+    fill_row_table(h->Mf, w.rowt);
     e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
   }
   if (e != hipSuccess) {

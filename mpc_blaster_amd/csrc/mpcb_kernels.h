@@ -13,6 +13,14 @@ constexpr int NZ = NX + NU;      // directions per instance = lanes per instance
 constexpr int GROUPS = 64 / NZ;  // instances per wavefront (4)
 constexpr int NBOX_XTRA = 18;    // per-lane box-mode scratch values per stage (see solve kernel)
 
+// Slots of a lane's record in Weights::rowt (the row rollout's lane constants, mpcb_row.h): the
+// gyroscopic form G, the J^-1 mixer row Lm, the gravity part of f's constant term, the tangent's
+// dT·minv, J^-1 M(e_u) and kd, and the lane's row of J.  What the diagonal-inertia tangent rollout
+// keeps comes first (slots 0..14: seven pairs and one value, so no loaded register is dead there);
+// slot 15 is padding; G[0..2] and the row of J (general inertia, captured scalars) follow.
+enum { ROWT_G3 = 0, ROWT_LM = 3, ROWT_GRAV = 7, ROWT_DSL = 8, ROWT_JU = 9, ROWT_KD = 12,
+       ROWT_J = 16, ROWT_G0 = 19, ROW_TAB_W = 22 };
+
 // Device-resident weights (row-major), uploaded once per handle.
 template <class T>
 struct Weights {
@@ -30,6 +38,10 @@ struct Weights {
   // qnc[j * NX + i] = QN[i][j] (zero for the input lanes j >= NX)
   alignas(16) T swt[NZ * NZ];
   alignas(16) T qnc[NZ * NX];
+  // lane-ordered table of the row rollout's prologue (row_body): rowt[t * ROW_TAB_W + ROWT_*] is
+  // what row lane t built from the model with selects on t in every wave; it depends on the
+  // handle and the lane only (T_blast and the wind stay in the kernel)
+  alignas(16) T rowt[NZ * ROW_TAB_W];
 };
 
 template <class T>

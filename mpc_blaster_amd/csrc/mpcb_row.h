@@ -147,123 +147,121 @@ __device__ __forceinline__ void row_body(const SplitArgs<T>& a) {
   const Model<T>& M = a.M;
   const T h = a.h, h2 = T(0.5) * a.h, h6 = a.h / T(6);
 
-  // ---- loop-invariant per-lane coefficients (0/1 row selectors, J-dependent forms) ----------
-  const T kv = T(t < 3);                   // f_t = v_t (t < 3), from lane t + 6
-  const T k1 = T(t == 3);                  // f_3 = wx + tt a
-  const T k2 = T(t == 3), k3 = T(t == 5);  // f_5 = ict a
-  const T k4 = T(t == 4);                  // f_4 = b
-  const T kr0 = T(t == 6), kr1 = T(t == 7), kr2 = T(t == 8);   // f_{6+i} = s r_i + const
-  // body rates t = 9..11: f = J^-1 M(u) - J^-1 (w x J w).  (w x Jw)_i = sum_jl B_i[j][l] w_j w_l
-  // with B_i[j][l] = sum_m eps_ijm J_ml; the per-lane form over the products
-  // p = (w0 w0, w1 w1, w2 w2, w0 w1, w0 w2, w1 w2) is G_t,p = -sum_i Jinv[t-9][i] coef_i,p
-  T G[6];
-  T Lm[4];   // J^-1 mixer: f_t's constant part is sum_m Lm[m] u_m
-  {
-    const int r = (t >= 9 && t < 12) ? t - 9 : -1;
-    T coef[3][6];
-    auto Jm = [&](int m, int l) { return M.J[m * 3 + l]; };
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;   // eps_{i,i1,i2} = +1, eps_{i,i2,i1} = -1
-      auto B = [&](int j, int l) {
-        return (j == i1 ? Jm(i2, l) : T(0)) - (j == i2 ? Jm(i1, l) : T(0));
-      };
-      coef[i][0] = B(0, 0); coef[i][1] = B(1, 1); coef[i][2] = B(2, 2);
-      coef[i][3] = B(0, 1) + B(1, 0); coef[i][4] = B(0, 2) + B(2, 0); coef[i][5] = B(1, 2) + B(2, 1);
-    }
-    // mixer (blastermodel.py:95-101): M = [ly(u1+u3-u0-u2), lx(u1+u2-u0-u3), c(u2+u3-u0-u1)]
-    const T mix[3][4] = {{-M.ly, M.ly, -M.ly, M.ly}, {-M.lx, M.lx, M.lx, -M.lx}, {-M.c, -M.c, M.c, M.c}};
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      T g = T(0);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) g += (r >= 0 ? M.Jinv[r * 3 + i] : T(0)) * coef[i][p];
-      G[p] = -g;
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      T l = T(0);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) l += (r >= 0 ? M.Jinv[r * 3 + i] : T(0)) * mix[i][m];
-      Lm[m] = l;
-    }
-  }
-  // the lane's row of J (captured J w, mpcb_model.h f_nom_lin c[14..16]) on lanes 9..11
-  const int jr = (t >= 9 && t < 12) ? t - 9 : 0;
-  const T J0 = M.J[jr * 3], J1 = M.J[jr * 3 + 1], J2 = M.J[jr * 3 + 2];
-  // constant part of f_t: the wind force / m and gravity (t = 6..8)
-  T K0 = T(0);
-  if (a.wind && t >= 6 && t < 9) K0 = a.wind[b * a.wind_sb + (t - 6)] * M.minv;
-  if (t == 8) K0 -= M.g;
-  const typename ScOf<T>::type kc;
-  const typename ScOf<T>::sa sa;
-  // the tangent's lane constants (TAN): direction e_t; its input part e_{t-12} on lanes 12..15
-  TanConst<T> K{};
-  T ev[NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) ev[i] = T(t == i);
-  if constexpr (TAN) {
-    const int m = t >= NX ? t - NX : -1;
-    K.dsl = m >= 0 ? M.minv : T(0);
-    const T mixm[3] = {m < 0 ? T(0) : ((m == 1 || m == 3) ? M.ly : -M.ly),
-                       m < 0 ? T(0) : ((m == 1 || m == 2) ? M.lx : -M.lx),
-                       m < 0 ? T(0) : ((m == 2 || m == 3) ? M.c : -M.c)};
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      K.Ju[r] = fma(M.Jinv[r * 3], mixm[0], fma(M.Jinv[r * 3 + 1], mixm[1], M.Jinv[r * 3 + 2] * mixm[2]));
-    K.kd[0] = -M.Jinv[0] * (M.J[8] - M.J[4]);
-    K.kd[1] = -M.Jinv[4] * (M.J[0] - M.J[8]);
-    K.kd[2] = -M.Jinv[8] * (M.J[4] - M.J[0]);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { K.J[i] = M.J[i]; K.Ji[i] = M.Jinv[i]; }
-  }
-  const int tv = var_index(t);             // the lane's variable column of [A|B] (-1: constant)
-  const bool exp_lane = TAN && tv >= 0 && c_raw < nb;
-
   // ---- workspace addressing: the quad-blocked records of mpcb_split.h soa(), quad qd --------
   T* const xu0 = a.XU + qd * XU_REC * SS + q;
   T* const cc0 = TAN ? nullptr : a.CC + qd * CCS_REC * SS + q;
   T* const gp0 = ITER ? a.GP + qd * GP_REC * SS + q : nullptr;
   const int64_t xu_k = nq * XU_REC * SS, cc_k = nq * CCS_REC * SS, gp_k = nq * GP_REC * SS;
 
+  // ---- the prologue's loads, all issued before the first wait: x0, the lane's table record, the
+  // wave's per-stage inputs ------------------------------------------------------------------
+  // X: x_t (t < 12) / u_{t-12} (t >= 12) of the interval's start
+  T X = T(0);
+  if (!ITER && t < NX) X = a.x0[b * a.x0_sb + t];
+  // The lane's J-dependent coefficients depend on the handle and the lane only: mpcb_create fills
+  // them once (mpcb_capi.hip fill_row_table, Weights::rowt) and the lane reads its record with
+  // 16-byte loads.  (Built here, they cost every wave ~40 exec-masked loads of the model, each
+  // behind its own branch, and their selects.)
+  // (Pairs, 16 bytes at fp64, and slot 14 alone: a loaded register that nothing reads is
+  // reused at once, and that write waits for the load.)
+  T rt[ROW_TAB_W];
+  {
+    const T* const rp = a.W->rowt + t * ROW_TAB_W;
+    ldv<T, 14, 2 * sizeof(T)>(rp, rt);
+    rt[14] = rp[14];
+    ldv<T, 6, 2 * sizeof(T)>(rp + ROWT_J, rt + ROWT_J);
+  }
   // The wave's per-stage inputs (rollout: u_ref; iterate: xbar, ubar) staged in LDS once
   // (row_lds_elems): a per-interval global load here sat on the chain, and its vmcnt(0) wait
   // also drained the previous interval's stores -- 24 % of the wave's cycles parked (PMC).
   extern __shared__ __attribute__((aligned(16))) unsigned char row_dyn[];
   T* const lu = reinterpret_cast<T*>(row_dyn);          // [GROUPS][N][NU]: u of the stage
   T* const lx = lu + GROUPS * N * NU;                    // ITER: [GROUPS][N + 1][NX]: xbar
-  // X: x_t (t < 12) / u_{t-12} (t >= 12) of the interval's start; x0's load is issued first
-  T X = T(0);
-  if (!ITER && t < NX) X = a.x0[b * a.x0_sb + t];
   {
-    // eight loads in flight per lane before their LDS writes (one at a time, the staging was a
-    // chain of global-load round trips: 2.5 us of the c2 wave's prologue), the group by compares
-    auto stage_in = [&](T* dst, const int per, auto&& src) {
-      const int total = GROUPS * per;
-      for (int e0 = lane; e0 < total; e0 += 64 * 8) {
-        T v[8];
+    // Row q copies its own instance's record: `per` contiguous values from one base pointer, as
+    // 16-byte vectors, eight loads in flight per lane before their LDS writes (one at a time, the
+    // staging was a chain of global-load round trips: 2.5 us of the c2 wave's prologue).  A ragged
+    // quad's spare rows copy the last instance again (c), a broadcast u_ref (stride 0) the same
+    // record four times.  A lane past the record's end copies its last vector again (the same
+    // value to the same slot), so a pass has no lane branches.  Records of up to 128 vectors
+    // (fp64: N <= 64) take one pass outside any loop, whose header would wait for the table's
+    // loads before issuing these.  The caller's records are only element-aligned.
+    constexpr int W = 16 / sizeof(T);
+    typedef T VG __attribute__((ext_vector_type(W), aligned(sizeof(T))));
+    typedef T VL __attribute__((ext_vector_type(W)));
+    auto stage_pass = [&](VL* d, const VG* s, const unsigned v0, const unsigned last) {
+      VL v[8];
+      unsigned i[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = e0 + 64 * u;
-          const int g = (e >= per) + (e >= 2 * per) + (e >= 3 * per);
-          const int64_t cg = qd * SS + g < nb ? qd * SS + g : nb - 1;
-          v[u] = e < total ? src(a.b0 + cg, e - g * per) : T(0);
-        }
+      for (int u = 0; u < 8; ++u) {
+        const unsigned e = v0 + 16 * u + t;
+        i[u] = e < last ? e : last;
+        v[u] = s[i[u]];
+      }
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (e0 + 64 * u < total) dst[e0 + 64 * u] = v[u];
+      for (int u = 0; u < 8; ++u) d[i[u]] = v[u];
+    };
+    auto stage_in = [&](T* dst, const int per, const T* src) {
+      const unsigned nv = per / W;
+      const VG* const s = reinterpret_cast<const VG*>(src);
+      VL* const d = reinterpret_cast<VL*>(dst + q * per);
+      if (nv <= 16 * 8) {
+        stage_pass(d, s, 0, nv - 1);
+      } else {
+#pragma nounroll
+        for (unsigned v0 = 0; v0 < nv; v0 += 16 * 8) stage_pass(d, s, v0, nv - 1);
       }
     };
-    static_assert(GROUPS == 4, "stage_in's group compares");
+    static_assert(NU % 4 == 0 && NX % 4 == 0, "stage_in copies whole 16-byte vectors");
     const int nu_e = N * NU, nx_e = (N + 1) * NX;
     if constexpr (ITER) {
-      stage_in(lu, nu_e, [&](int64_t bb, int r) { return a.ubar[bb * (int64_t)nu_e + r]; });
-      stage_in(lx, nx_e, [&](int64_t bb, int r) { return a.xbar[bb * (int64_t)nx_e + r]; });
+      stage_in(lu, nu_e, a.ubar + b * (int64_t)nu_e);
+      stage_in(lx, nx_e, a.xbar + b * (int64_t)nx_e);
     } else {
-      stage_in(lu, nu_e, [&](int64_t bb, int r) { return a.uref[bb * a.uref_sb + r]; });
+      stage_in(lu, nu_e, a.uref + b * a.uref_sb);
     }
     wave_lds_sync();
   }
+
+  // ---- loop-invariant per-lane coefficients (0/1 row selectors, J-dependent forms) ----------
+  // the tangent's direction e_t (TAN); the row selectors of f are among its components
+  T ev[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) ev[i] = T(t == i);
+  const T kv = T(t < 3);                   // f_t = v_t (t < 3), from lane t + 6
+  const T k1 = ev[3];                      // f_3 = wx + tt a
+  const T k2 = ev[3], k3 = ev[5];          // f_5 = ict a
+  const T k4 = ev[4];                      // f_4 = b
+  const T kr0 = ev[6], kr1 = ev[7], kr2 = ev[8];   // f_{6+i} = s r_i + const
+  // body rates t = 9..11: f = J^-1 M(u) - J^-1 (w x J w).  (w x Jw)_i = sum_jl B_i[j][l] w_j w_l
+  // with B_i[j][l] = sum_m eps_ijm J_ml; the per-lane form over the products
+  // p = (w0 w0, w1 w1, w2 w2, w0 w1, w0 w2, w1 w2) is G_t,p = -sum_i Jinv[t-9][i] coef_i,p
+  T G[6];
+  T Lm[4];   // J^-1 mixer: f_t's constant part is sum_m Lm[m] u_m
+#pragma unroll
+  for (int p = 0; p < 3; ++p) { G[p] = rt[ROWT_G0 + p]; G[p + 3] = rt[ROWT_G3 + p]; }
+#pragma unroll
+  for (int m = 0; m < 4; ++m) Lm[m] = rt[ROWT_LM + m];
+  // the lane's row of J (captured J w, mpcb_model.h f_nom_lin c[14..16]) on lanes 9..11
+  const T J0 = rt[ROWT_J], J1 = rt[ROWT_J + 1], J2 = rt[ROWT_J + 2];
+  // constant part of f_t: the wind force / m (t = 6..8) less gravity (the table's slot holds g on
+  // lane 8 and 0 elsewhere: x - 0 is x, sign of zero included)
+  T Kw = T(0);
+  if (a.wind && t >= 6 && t < 9) Kw = a.wind[b * a.wind_sb + (t - 6)] * M.minv;
+  const T K0 = Kw - rt[ROWT_GRAV];
+  const typename ScOf<T>::type kc;
+  const typename ScOf<T>::sa sa;
+  // the tangent's lane constants (TAN): its input part e_{t-12} on lanes 12..15
+  TanConst<T> K{};
+  if constexpr (TAN) {
+    K.dsl = rt[ROWT_DSL];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { K.Ju[r] = rt[ROWT_JU + r]; K.kd[r] = rt[ROWT_KD + r]; }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { K.J[i] = M.J[i]; K.Ji[i] = M.Jinv[i]; }
+  }
+  const int tv = var_index(t);             // the lane's variable column of [A|B] (-1: constant)
+  const bool exp_lane = TAN && tv >= 0 && c_raw < nb;
   const T* const lxq = lx + q * (N + 1) * NX;
   const T* const luq = lu + q * N * NU;
   if (ITER && t < NX) X = lxq[t];

@@ -512,9 +512,11 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   // fp64 and the fp32 export instantiation: the model constants of the tangent (J, Jinv, arm
   // lengths, 1/m) as opaque loop-invariant VGPRs instead of kernel-argument SGPRs (MPCB_P2_MVGPR,
   // default on): scalar registers the body otherwise spills to VGPR lanes and reads back at every
-  // stage (fp64 22 -> 0 spills, fp32 export 14 -> 0)
+  // stage (fp64 22 -> 0 spills, fp32 export 14 -> 0).  Only where the body integrates the tangent:
+  // with TIN nothing reads them, and pinning them still cost 44 copies, their kernel-argument
+  // loads and, in the fused kernel, waits on the rollout's last export stores.
   Model<T> Mv = a.M;
-  if constexpr ((sizeof(T) == 8 || EXPORT) && MPCB_P2_MVGPR) {
+  if constexpr ((sizeof(T) == 8 || EXPORT) && MPCB_P2_MVGPR && !TIN) {
     asm volatile("" : "+v"(Mv.minv), "+v"(Mv.lx), "+v"(Mv.ly), "+v"(Mv.c));
 #pragma unroll
     for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(Mv.J[i]), "+v"(Mv.Jinv[i]));
@@ -544,6 +546,10 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
   const int64_t rstep = a.imajor ? 1 : nq4 * SS;   // rec2 records per stage
   const T* pcol = nullptr; const T* pxu = nullptr; const T* pref = nullptr; const T* pgpp = nullptr;
   T* pkr = nullptr;
+  // DT: the lane's PS2 row of stage 0 (box path snapshots); stage k lies k uniform steps above it,
+  // so the stage's share of the address is scalar arithmetic (taken from rec2(k), every stage
+  // stepped a per-lane 64-bit counter with three vector instructions, snapshots or not)
+  T* pps0 = nullptr;
   int64_t scol = 0, sref = 0;
   auto load_stage = [&]() {
 #pragma unroll
@@ -574,6 +580,7 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
       sref = j < NX ? NX : NU;
       if (iterate) pgpp = soa(a.GP, N - 1, GP_REC, nb, c) + jx * SS;
       pkr = rec2(a.KR, N - 1, KR2_REC, nb, c, N, a.imajor) + (j <= NX ? j : NX + 1);
+      if (EXPORT && a.PS) pps0 = rec2(a.PS, 0, PS2_REC, nb, c, N, a.imajor) + jx * PS2_W;
       load_stage();
     }
 #pragma unroll
@@ -926,7 +933,8 @@ __device__ __forceinline__ void riccati_body(const SplitArgs<T>& a, const int64_
         ps[d] = L.X[(o > j ? o : j) * XS + (o > j ? j : o)];
       }
       ps[7] = pn;
-      stv<T, PS2_W>(rec2(a.PS, k, PS2_REC, nb, c, N, a.imajor) + j * PS2_W, ps);
+      if constexpr (DT) stv<T, PS2_W>(pps0 + (int64_t)k * (rstep * PS2_REC), ps);
+      else stv<T, PS2_W>(rec2(a.PS, k, PS2_REC, nb, c, N, a.imajor) + j * PS2_W, ps);
     }
     STAMP(8);
     if constexpr (D64) {
