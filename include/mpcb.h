@@ -164,6 +164,36 @@ int mpcb_linearize(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar
                    void* A, void* Bm, void* xnext, void* hip_stream);
 
 /*
+ * Quality of a given iterate (X [B,N+1,nx], U [B,N,nu], contiguous; e.g. what a solve returned):
+ * the objective and the KKT residuals per instance.  Replaces ``ocp_solver.get_cost()``
+ * (simulation_blaster.py:86, mavros_blaster_sim.py:87) and acados' ``get_residuals()``.  Reads the
+ * handle's weights, boxes, model, wind and 17/6 parameters as mpcb_solve_iterate does; s =
+ * cfg.cost_scale.  Outputs are [B] arrays of the handle's dtype; any may be NULL, not all four.
+ *   cost      1/2 s sum_{k<N} (|x_k - xref_k|^2_Q + |u_k - uref_k|^2_R) + 1/2 |x_N - xref_N|^2_QN
+ *   res_eq    max_k |Phi(x_k, u_k) - x_{k+1}|_inf (the handle's RK4 step); with x0 [B,nx] given
+ *             (may be NULL) also |x_0 - x0|_inf
+ *   res_ineq  the largest violation of lbu <= u_k <= ubu (k < N, box_u) and of lbx <= x_k <= ubx
+ *             (0 < k < N, box_x); never negative, 0 without boxes
+ *   res_stat  the natural residual of the reduced gradient: lambda_N = QN (x_N - xref_N), and for
+ *             k = N-1 .. 0, with A_k, B_k the exact RK4 sensitivities at (x_k, u_k),
+ *               g_k = s R (u_k - uref_k) + B_k^T lambda_{k+1},
+ *               lambda_k = s Q (x_k - xref_k) + A_k^T lambda_{k+1};
+ *             res_stat = max_k |g_k|_inf, with box_u max_k |u_k - clip(u_k - g_k, lbu, ubu)|_inf.
+ *             It is the gradient of the single-shooting objective when res_eq = 0, and merges
+ *             stationarity with the input box's complementarity (no tolerance).  With box_x a
+ *             non-NULL res_stat is MPCB_E_UNSUPPORTED: the state multipliers are not available.
+ * An instance with a non-finite input gets NaN in every output; other instances are unaffected.
+ */
+int mpcb_eval(mpcb_handle* h, int64_t B,
+              const void* x0, int64_t x0_sb,
+              const void* X, const void* U,
+              const void* xref, int64_t xref_sb,
+              const void* uref, int64_t uref_sb,
+              const void* wind, int64_t wind_sb,
+              void* cost, void* res_eq, void* res_ineq, void* res_stat,
+              void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */

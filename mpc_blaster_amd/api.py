@@ -172,6 +172,33 @@ class BatchedMPC:
             self._ptr(self._U), self._ptr(self._status), self._stream()))
         return self._u0
 
+    def evaluate(self, X, U, x_ref, u_ref, x0=None, wind=None, stat=True):
+        """Cost and KKT residuals of the iterate (X [B,N+1,nx], U [B,N,nu]) per instance
+        (mpcb_eval; acados ``get_cost()`` / ``get_residuals()``): a dict of [B] device tensors
+        ``cost``, ``res_eq`` (dynamics defect; with ``x0`` also |x_0 - x0|), ``res_ineq`` (box
+        violation) and, unless ``stat=False``, ``res_stat`` (natural residual of the reduced
+        gradient; needs the adjoint sweep, unsupported with the state box).  Asynchronous, like
+        ``solve``."""
+        torch = _torch()
+        N = self.cfg.N
+        Xd, _ = self._dev(X, (N + 1, self.nx), 'X')
+        B = Xd.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        Ud, _ = self._dev(U, (N, self.nu), 'U', B)
+        xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
+        ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
+        x0d, x0_sb = (None, 0) if x0 is None else self._dev(x0, (self.nx,), 'x0', B)
+        wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
+        out = {k: torch.empty((B,), dtype=self.dtype, device=self._tdev)
+               for k in ('cost', 'res_eq', 'res_ineq') + (('res_stat',) if stat else ())}
+        self._keep_eval = (Xd, Ud, xr, ur, x0d, wd)
+        _lib.check(self.lib.mpcb_eval(
+            self._h, B, self._ptr(x0d), x0_sb, self._ptr(Xd), self._ptr(Ud), self._ptr(xr), xr_sb,
+            self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(out['cost']), self._ptr(out['res_eq']),
+            self._ptr(out['res_ineq']), self._ptr(out.get('res_stat')), self._stream()))
+        return out
+
     def set_params(self, p):
         """Parameters of the full 17/6 model (acados ``set(k, 'p', p)``,
         simulation_blaster.py:65-69): column-major J_angles 3x2, J_euler 3x3, J_p 3x3, T_blast.

@@ -11,8 +11,12 @@ from .api import BatchedMPC
 
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
-                xbar=None, ubar=None):
-    """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps)."""
+                xbar=None, ubar=None, diagnostics=False):
+    """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
+
+    ``diagnostics=True`` evaluates the new iterate after each solve (``BatchedMPC.evaluate`` with
+    that step's x0) and returns a fourth value: a dict of [B, nsim] tensors ``cost``, ``res_eq``,
+    ``res_stat`` (without ``res_stat`` on a handle with a state box)."""
     import torch
     dev = f'cuda:{mpc.device}'
     dt = mpc.dtype
@@ -29,10 +33,19 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     Xs = torch.empty((B, nsim + 1, NX), dtype=dt, device=dev)
     Us = torch.empty((B, nsim, NU), dtype=dt, device=dev)
     Xs[:, 0] = x
+    stat = mpc.cfg.lbx is None
+    diag = {k: torch.empty((B, nsim), dtype=dt, device=dev)
+            for k in ('cost', 'res_eq') + (('res_stat',) if stat else ())} if diagnostics else None
     for i in range(nsim):
         mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st))
         worst = torch.maximum(worst, st)
         Us[:, i] = u0
+        if diagnostics:
+            ev = mpc.evaluate(xb, ub, x_ref, u_ref, x0=x, wind=wind, stat=stat)
+            for k, v in diag.items():
+                v[:, i] = ev[k]
         x = mpc.sim_step(x, u0, T=plant_T, wind=wind)
         Xs[:, i + 1] = x
+    if diagnostics:
+        return Xs, Us, worst, diag
     return Xs, Us, worst

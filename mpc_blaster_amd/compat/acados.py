@@ -65,7 +65,8 @@ def _slice_y(v, B, name, nx=NX, nu=NU):
 
 
 class AcadosOcpSolver:
-    """``AcadosOcpSolver`` subset: set / cost_set / solve / get / get_cost (B instances)."""
+    """``AcadosOcpSolver`` subset: set / cost_set / solve / get / get_cost / get_residuals
+    (B instances)."""
 
     def __init__(self, config: MPCConfig, batch: int = 1, device: int = 0, json_file=None):
         from ..api import BatchedMPC
@@ -180,21 +181,33 @@ class AcadosOcpSolver:
             raise KeyError(f'field {field!r} not supported')
         return v[0] if self.B == 1 else v
 
-    def get_cost(self):
-        """Objective at the current iterate (what acados' get_cost() evaluates)."""
+    def _evaluate(self, stat):
         torch = _torch()
-        dt = self.xbar.dtype
-        Q = torch.as_tensor(self.cfg.Q, dtype=dt, device=self._dev)
-        R = torch.as_tensor(self.cfg.R, dtype=dt, device=self._dev)
-        QN = torch.as_tensor(self.cfg.QN, dtype=dt, device=self._dev)
-        yr = torch.as_tensor(self.yref, dtype=dt, device=self._dev)
-        ex = self.xbar[:, :-1] - yr[:, :-1, :self.nx]
-        eu = self.ubar - yr[:, :-1, self.nx:]
-        eN = self.xbar[:, -1] - yr[:, -1, :self.nx]
-        c = 0.5 * self.cfg.scale * (torch.einsum('bki,ij,bkj->b', ex, Q, ex) + torch.einsum('bki,ij,bkj->b', eu, R, eu))
-        c = c + 0.5 * torch.einsum('bi,ij,bj->b', eN, QN, eN)
-        c = c.cpu().numpy()
+        if self._p_dirty:
+            self._upload_params()
+        out = self.mpc.evaluate(self.xbar, self.ubar, self.yref[:, :, :self.nx],
+                                self.yref[:, :self.N, self.nx:], x0=self.x0, stat=stat)
+        torch.cuda.synchronize(self.mpc.device)
+        return {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+
+    def get_cost(self):
+        """Objective at the current iterate (what acados' get_cost() evaluates), on the device
+        (mpcb_eval)."""
+        c = self._evaluate(stat=False)['cost']
         return float(c[0]) if self.B == 1 else c
+
+    def get_residuals(self):
+        """acados' ``get_residuals()`` 4-vector [res_stat, res_eq, res_ineq, res_comp] at the
+        current iterate with the facade's x0 and yref ([B, 4] for ``batch`` > 1; include/mpcb.h
+        mpcb_eval defines the entries).  ``res_comp`` is NaN: slot 0 is the natural residual of
+        the reduced gradient, which already contains the input box's complementarity, and the
+        solver exports no multipliers to form a separate one from.  With a state box ``res_stat``
+        is NaN too (the state multipliers are not available)."""
+        stat = self.cfg.lbx is None
+        o = self._evaluate(stat=stat)
+        nan = np.full(self.B, np.nan)
+        r = np.stack([o['res_stat'] if stat else nan, o['res_eq'], o['res_ineq'], nan], axis=1)
+        return r[0] if self.B == 1 else r
 
 
 class AcadosSimSolver:

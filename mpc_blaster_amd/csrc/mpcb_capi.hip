@@ -829,6 +829,59 @@ extern "C" int mpcb_linearize(mpcb_handle* h, int64_t B, const void* xbar, const
   return MPCB_OK;
 }
 
+template <class T>
+static int eval_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* X, const void* U,
+                     const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
+                     const void* wind, int64_t wind_sb, void* cost, void* res_eq, void* res_ineq,
+                     void* res_stat, void* stream) {
+  EvalArgs<T> a;
+  a.B = B;
+  a.N = h->cfg.N;
+  a.box_u = h->cfg.box_u;
+  a.box_x = h->cfg.box_x;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = h->weights;
+  a.p = nullptr; a.p_sb = a.p_kb = 0;
+  if (h->full) {   // the parameters mpcb_solve_iterate reads: mpcb_set_params' array or the defaults
+    a.p = h->params ? (const T*)h->params : reinterpret_cast<const Weights17<T>*>(h->weights)->p;
+    a.p_sb = h->params ? h->params_sb : 0;
+    a.p_kb = h->params ? h->params_kb : 0;
+  }
+  a.x0 = (const T*)x0; a.x0_sb = x0_sb;
+  a.X = (const T*)X; a.U = (const T*)U;
+  a.xref = (const T*)xref; a.xref_sb = xref_sb;
+  a.uref = (const T*)uref; a.uref_sb = uref_sb;
+  a.wind = (const T*)wind; a.wind_sb = wind_sb;
+  a.cost = (T*)cost; a.res_eq = (T*)res_eq; a.res_ineq = (T*)res_ineq; a.res_stat = (T*)res_stat;
+  const hipError_t e = h->full ? launch_eval17<T>(a, (hipStream_t)stream) : launch_eval<T>(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "eval launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* X, const void* U,
+                         const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
+                         const void* wind, int64_t wind_sb, void* cost, void* res_eq, void* res_ineq,
+                         void* res_stat, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (!cost && !res_eq && !res_ineq && !res_stat) return fail(MPCB_E_INVALID, "no output requested");
+  if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
+  if (h->cfg.box_x && res_stat)
+    return fail(MPCB_E_UNSUPPORTED, "res_stat is unsupported with box_x: the state multipliers are not available");
+  if (B == 0) return MPCB_OK;
+  if (!X || !U || !xref || !uref) return fail(MPCB_E_INVALID, "X, U, xref and uref are required");
+  if (int rc = check_params(h, B)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->cfg.dtype == MPCB_F64)
+    return eval_impl<double>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, cost, res_eq,
+                             res_ineq, res_stat, stream);
+  return eval_impl<float>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, cost, res_eq,
+                          res_ineq, res_stat, stream);
+}
+
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
                   int64_t wind_sb, double T, void* x_out, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");

@@ -195,6 +195,96 @@ __device__ __forceinline__ void rk4_17(const T* __restrict__ x, const T* __restr
   }
 }
 
+// DPP row broadcast (v_mov_b32_dpp row_newbcast): lane L of every 16-lane row hands v to the row.
+template <int L> __device__ __forceinline__ float rowbc(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x150 + L, 0xF, 0xF, true));
+}
+template <int L> __device__ __forceinline__ double rowbc(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)b, 0x150 + L, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), 0x150 + L, 0xF, 0xF, true);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// sin/cos of the five angles with 16 lanes per instance: lane t < 5 evaluates the pair of angle t
+// and the row broadcast hands the ten values to the row
+struct Trig17Row {
+  int t;   // lane in the 16-lane row
+  template <class T>
+  __device__ __forceinline__ void operator()(const T* __restrict__ x, T (&sn)[5], T (&cs)[5]) const {
+    const uint64_t m1 = lane_mask(t == 1), m2 = lane_mask(t == 2), m3 = lane_mask(t == 3), m4 = lane_mask(t == 4);
+    T ang = csel(m1, x[4], x[3]);
+    ang = csel(m2, x[5], ang);
+    ang = csel(m3, x[12], ang);
+    ang = csel(m4, x[13], ang);
+    T s0, c0;
+    sc(ang, &s0, &c0);
+    sn[0] = rowbc<0>(s0); cs[0] = rowbc<0>(c0);
+    sn[1] = rowbc<1>(s0); cs[1] = rowbc<1>(c0);
+    sn[2] = rowbc<2>(s0); cs[2] = rowbc<2>(c0);
+    sn[3] = rowbc<3>(s0); cs[3] = rowbc<3>(c0);
+    sn[4] = rowbc<4>(s0); cs[4] = rowbc<4>(c0);
+  }
+};
+
+// ---- the linearisation of one interval with 16 lanes per (instance, stage) --------------------
+constexpr int LQ17 = 16, GQ17 = 64 / LQ17;
+
+// One (instance, stage) of the packed linearisation, lane t < 16: column j of [A_k | B_k] into
+// col(j, v[17]) and, on lane 0, the RK4 successor into succ(xn[17]).  Shared by the workspace
+// kernel (lin17ws_kernel), the dense debug export (linearize17_kernel, mpcb_linearize) and the
+// adjoint sweep of mpcb_eval (mpcb_eval.hip), so the parity test of mpcb_linearize covers the
+// arithmetic the solver runs.
+template <class T, class Col, class Succ>
+__device__ __forceinline__ void lin17_packed(int t, const T* pb, T h, const Model<T>& M, const T* xk,
+                                             const T* uk, Col&& colf, Succ&& succ) {
+  if (t >= 14) {
+    if (t == 14) {   // position and POC-state directions
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        const int jj = q < 3 ? q : 11 + q;
+        T v[NX17];
+#pragma unroll
+        for (int i = 0; i < NX17; ++i) v[i] = (i == jj) ? T(1) : T(0);
+        colf(jj, v);
+      }
+    } else {         // velocity directions
+      P17<T> P;
+      unpack_p17(pb, P);
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) {
+        const int jj = 6 + cc;
+        T v[NX17];
+#pragma unroll
+        for (int i = 0; i < NX17; ++i) {
+          v[i] = (i == jj) ? T(1) : T(0);
+          if (i == cc) v[i] = h;
+          if (i >= 14) v[i] = h * P.Jp[(i - 14) * 3 + cc];
+        }
+        colf(jj, v);
+      }
+    }
+    return;
+  }
+  const int j = t < 3 ? 3 + t : (t < 8 ? 6 + t : 9 + t);   // 3..5, 9..13, 17..22
+  P17<T> P;
+  unpack_p17(pb, P);
+  T x[NX17], u[NU17], dx[NX17], du[NU17], xn[NX17], col[NX17];
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) {
+    x[i] = xk[i];
+    dx[i] = (j == i) ? T(1) : T(0);
+  }
+#pragma unroll
+  for (int m = 0; m < NU17; ++m) {
+    u[m] = uk[m];
+    du[m] = (j == NX17 + m) ? T(1) : T(0);
+  }
+  // the five sin/cos of the nominal point: lane t < 5 of the row evaluates one (Trig17Row)
+  rk4_17<T, true>(x, dx, u, du, h, M, P, xn, col, Trig17Row{t});
+  colf(j, col);
+  if (t == 0) succ(xn);
+}
+
 // Device-resident weights of the 17/6 OCP (row-major) and the default parameter vector.
 template <class T>
 struct Weights17 {
@@ -347,5 +437,6 @@ hipError_t launch_linearize17(int64_t B, int N, T h, const Model<T>& M, const T*
 template <class T>
 hipError_t launch_sim_step17(int64_t B, T h, const Model<T>& M, const T* p, int64_t p_sb,
                              const T* x, const T* u, T* xo, hipStream_t st);
+template <class T> hipError_t launch_eval17(const EvalArgs<T>& a, hipStream_t st);   // mpcb_eval.hip
 
 }  // namespace mpcb

@@ -215,6 +215,25 @@ template <class T>
 hipError_t launch_linearize(int64_t B, int N, T h, const Model<T>& M, const T* xbar,
                             const T* ubar, const T* wind, int64_t wind_sb, T* A, T* Bm,
                             T* xnext, hipStream_t st);
+// mpcb_eval (mpcb_eval.hip): cost and KKT residuals of a given iterate, both models.  Not a solve:
+// its kernels are launched outside the launch log.
+template <class T>
+struct EvalArgs {
+  int64_t B;
+  int N;
+  int box_u, box_x;
+  T h, s;
+  Model<T> M;
+  const void* W;                     // Weights<T> (12/4) or Weights17<T> (17/6)
+  const T* p; int64_t p_sb, p_kb;    // 17/6: parameters as in FullArgs, never null
+  const T* x0; int64_t x0_sb;        // nullable
+  const T* X; const T* U;            // [B, N+1, nx], [B, N, nu]
+  const T* xref; int64_t xref_sb;
+  const T* uref; int64_t uref_sb;
+  const T* wind; int64_t wind_sb;    // 12/4, nullable
+  T *cost, *res_eq, *res_ineq, *res_stat;   // [B] each, nullable; res_stat selects the adjoint sweep
+};
+template <class T> hipError_t launch_eval(const EvalArgs<T>& a, hipStream_t st);   // 12/4
 template <class T>
 hipError_t launch_sim_step(int64_t B, T h, const Model<T>& M, const T* x, const T* u,
                            const T* wind, int64_t wind_sb, T* xo, hipStream_t st);
