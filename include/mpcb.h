@@ -60,6 +60,10 @@ enum { MPCB_STATUS_OK = 0, MPCB_STATUS_NAN = 1, MPCB_STATUS_MAXITER = 2, MPCB_ST
  * blastThruster, statesBound, controlBound)`` constructor + ``generateController()``
  * (src/scripts/blastermodel.py:16, :214-292) that build the acados OCP.
  * Matrices are row-major, leading dimension nx (Q, QN) or nu (R).
+ * Q, R and QN must be symmetric: the kernels read them transposed in some tables and straight in
+ * others, so a config in which one of them differs from its transpose by more than
+ * 1e-12 * max|entry| is refused with MPCB_E_INVALID (by mpcb_create, mpcb_plan_kernels and
+ * mpcb_debug_row_table alike).  Dense symmetric weights are supported on every path.
  */
 typedef struct mpcb_config {
   int32_t nx;            /* 12 (rigid-body slice, the BASELINE configs) or 17 (full model) */

@@ -264,6 +264,23 @@ static int validate_config(const mpcb_config* cfg, int64_t max_batch, double Jin
   if (max_batch < 1) return fail(MPCB_E_INVALID, "max_batch=%lld", (long long)max_batch);
   if (cfg->box_u && cfg->max_as_iter < 1) return fail(MPCB_E_INVALID, "max_as_iter must be >= 1");
   if (!inv3(cfg->J, Jinv)) return fail(MPCB_E_INVALID, "inertia J is singular");
+  // the kernels load Q, R and QN transposed in some tables and straight in others (fill_weights'
+  // swt / qnc against W.Q[r * NX + cl]), so an asymmetric weight would give path-dependent answers
+  struct { const char* name; const double* m; int n; } const wts[3] = {
+      {"Q", cfg->Q, cfg->nx}, {"R", cfg->R, cfg->nu}, {"QN", cfg->QN, cfg->nx}};
+  for (const auto& w : wts) {
+    double big = 0, asym = 0;
+    int ai = 0, aj = 0;
+    for (int i = 0; i < w.n; ++i)
+      for (int j = 0; j < w.n; ++j) {
+        const double a = w.m[i * w.n + j], d = std::fabs(a - w.m[j * w.n + i]);
+        if (std::fabs(a) > big) big = std::fabs(a);
+        if (d > asym) asym = d, ai = i, aj = j;
+      }
+    if (asym > 1e-12 * big)
+      return fail(MPCB_E_INVALID, "%s is not symmetric: [%d][%d] and [%d][%d] differ by %.3g", w.name, ai, aj, aj, ai,
+                  asym);
+  }
   return MPCB_OK;
 }
 

@@ -521,7 +521,11 @@ def ipm_box_solve(A, Bm, gap, dx0, xbar, ubar, xref, uref, spec, max_iter=60, lb
     solution; without a state box IPM_SHORT_RUN / IPM_SHORT), or a non-finite iterate, or after
     ``max_iter`` iterations.  Returns dx, du, status, iterations.
     ``centring='adaptive'`` keeps this scheme for the input box alone (the 12/4 active set's
-    fallback, pdas_solve); otherwise the input box alone takes Mehrotra's predictor-corrector."""
+    fallback, pdas_solve); otherwise the input box alone takes Mehrotra's predictor-corrector.
+    At N = 1 the state box has no stage to constrain (stages 1..N-1 are none): the problem is the
+    input box's."""
+    if spec.N < 2:
+        lbx = ubx = None
     if lbx is None and centring != 'adaptive':   # the input box alone: _ipm_box_mehrotra
         return _ipm_box_mehrotra(A, Bm, gap, dx0, xbar, ubar, xref, uref, spec, max_iter=max_iter, trace=trace)
     Bsz, N = xbar.shape[0], spec.N

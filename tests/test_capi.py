@@ -83,6 +83,35 @@ def test_config_validation():
     assert list(cc.ubu)[:4] == [65.0] * 4
 
 
+@pytest.mark.parametrize('full', [False, True])
+def test_asymmetric_weights_are_refused(full):
+    """validate_config (through mpcb_plan_kernels, which needs no device): Q, R or QN differing
+    from its transpose by more than 1e-12 max|entry| is MPCB_E_INVALID (the kernels read the
+    weights transposed in some tables and straight in others); dense symmetric weights, and an
+    asymmetry at rounding level, are accepted."""
+    from mpc_blaster_amd import MPCConfig, _lib
+    make = MPCConfig.full if full else MPCConfig
+    nx, nu = (17, 6) if full else (12, 4)
+    rng = np.random.default_rng(5)
+
+    def spd(n, scale):
+        m = rng.normal(size=(n, n))
+        return scale * (m @ m.T / n + np.eye(n))
+
+    dense = dict(Q=spd(nx, 5.0), R=spd(nu, 0.1), QN=spd(nx, 50.0))
+    assert _lib.plan_kernels(make(N=4, **dense).to_c(), 8, 8)['riccati']
+    for name, n in (('Q', nx), ('R', nu), ('QN', nx)):
+        big = np.abs(dense[name]).max()
+        w = dense[name].copy()
+        w[n - 1, 0] += 1e-13 * big          # below the threshold: accepted
+        assert _lib.plan_kernels(make(N=4, **dict(dense, **{name: w})).to_c(), 8, 8)['riccati']
+        w[n - 1, 0] += 1e-11 * big          # last row, first column: the far corner of the matrix
+        with pytest.raises(_lib.MpcbError, match=f'mpcb error -1: {name} is not symmetric'):
+            _lib.plan_kernels(make(N=4, **dict(dense, **{name: w})).to_c(), 8, 8)
+        with pytest.raises(_lib.MpcbError, match=f'{name} is not symmetric'):
+            _lib.plan_kernels(make(N=4, **dict(dense, **{name: np.triu(dense[name])})).to_c(), 8, 8)
+
+
 def test_config_defaults_equal_reference_json_slice():
     """MPCConfig defaults = the 12/4 slice of acados_ocp_blasterModel.json (fixture)."""
     import json

@@ -160,6 +160,24 @@ def test_ipm_state_box_kkt():
     assert stat.max() <= 1e-12 and viol.max() <= 1e-10 and gap.max() <= 1e-8, (stat, viol, gap)
 
 
+def test_state_box_at_horizon_one_is_the_input_box_problem():
+    """N = 1 has no stage in 1..N-1, so the state box constrains nothing: mpc_solve17 returns the
+    input-box result bit for bit (it raised 'zero-size array to reduction operation maximum')."""
+    N, B = 1, 4
+    lbu = np.array([2.0, 0.0, 5.0, 1.0, -0.05, -0.12])
+    ubu = np.array([40.0, 65.0, 22.0, 50.0, 0.09, 0.03])
+    x0, _, p = _random_point(B, 7)
+    xref = np.zeros((B, N + 1, 17))
+    xref[..., 2] = 3.5
+    uref = np.zeros((B, N, 6))
+    uref[..., :4] = 22.0725
+    a = mpc_solve17(x0, xref, uref, FullSpec(N=N, lbu=lbu, ubu=ubu), p)
+    b = mpc_solve17(x0, xref, uref, FullSpec(N=N, lbu=lbu, ubu=ubu, lbx=np.full(17, -1e-3), ubx=np.full(17, 1e-3)), p)
+    assert (a['status'] == 0).all() and (b['status'] == 0).all()
+    assert np.array_equal(a['U'], b['U']) and np.array_equal(a['X'], b['X'])
+    assert ((np.abs(a['U'] - lbu) < 1e-6) | (np.abs(a['U'] - ubu) < 1e-6)).any()   # the box is active
+
+
 def test_ipm_state_box_thin_interior_instances_converge(monkeypatch):
     """The two LP-feasible bench instances whose Newton system breaks before mu = 1e-8
     (tests/golden/sbox_thin_interior.npz).  Without the polish the interior point's iterate at the

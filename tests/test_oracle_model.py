@@ -89,6 +89,34 @@ def test_rk4_sensitivities_match_central_differences():
         assert np.abs(S[:, :, j] - fd).max() < 1e-8
 
 
+def test_rk4_sensitivities_match_central_differences_alt_params():
+    """The same check under the ALT model constants of tests/alt_config.py (general inertia,
+    another mass, arms, drag constant, gravity and blaster thrust), dt = 0.05 and a wind force;
+    the tolerance of the default-parameter test above."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import alt_config as ac
+    rng = np.random.default_rng(2)
+    P = Params(**ac.model())
+    x = rng.uniform(-0.5, 0.5, (16, 12))
+    u = rng.uniform(5, 40, (16, 4))
+    w = rng.uniform(-5, 5, (16, 3))
+    h = ac.TIME['b']['dt']
+    _, A, B = rk4_sens(x, u, h, P, w)
+    S = np.concatenate([A, B], axis=2)
+    z = np.concatenate([x, u], axis=1)
+    eps = 1e-6
+    for j in range(16):
+        zp, zm = z.copy(), z.copy()
+        zp[:, j] += eps
+        zm[:, j] -= eps
+        fd = (rk4_step(zp[:, :12], zp[:, 12:], h, P, w) - rk4_step(zm[:, :12], zm[:, 12:], h, P, w)) / (2 * eps)
+        assert np.abs(S[:, :, j] - fd).max() < 1e-8
+    # ... and the constants matter: the default ones give other sensitivities
+    _, A0, B0 = rk4_sens(x, u, h, Params(), w)
+    assert np.abs(A - A0).max() > 1e-3 and np.abs(B - B0).max() > 1e-3
+
+
 def test_mathutils_known_answers():
     """utils/MathUtils.py helpers (unused by the path) vs the oracle restatement."""
     from oracle.mathutils import quat_multiply, unit_quat_inverse, quat_to_rot

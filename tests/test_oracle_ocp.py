@@ -113,3 +113,27 @@ def test_pdas_hands_slow_instances_to_the_interior_point():
                       o['ubar'][sel], inp['xref'][sel], inp['uref'][sel], spec)
     assert np.abs(o['ubar'][sel] + du - o['U'][sel]).max() < 1e-5
     assert (o['U'] >= -1e-9).all() and (o['U'] <= 65 + 1e-9).all()
+
+
+def test_pdas_equals_bvls_under_alt_config():
+    """The reference the GPU tests of tests/test_gpu_config.py lean on, under their ALT-a problem
+    definition (dense weights, another model, dt = 0.02, the per-channel box with lbu != 0): the
+    active set with its interior-point hand-over against the independent BVLS solve within 1e-9
+    (observed 1.6e-11), with the box genuinely active and some instances handed over."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import alt_config as ac
+    N, B = 6, 12
+    inp = make_inputs('c3', ids=np.arange(B, dtype=np.uint64), N=N)
+    spec = OcpSpec(N=N, **ac.spec_kwargs(ac.fields(alt='a', box='input')))
+    assert spec.params.mass == 6.5 and spec.dt == 0.02 and spec.s == 0.02 and spec.lbu[2] == 5.0
+    o = mpc_solve(inp['x0'], inp['xref'], inp['uref'], spec, return_lin=True)
+    assert (o['status'] == 0).all()
+    du = dense_box_qp(o['A'], o['B'], o['gap'], np.zeros((B, 12)), o['xbar'], o['ubar'],
+                      inp['xref'], inp['uref'], spec)
+    err = np.abs(o['ubar'] + du - o['U']).max()
+    on = (np.abs(o['U'] - spec.lbu) <= 1e-6) | (np.abs(o['U'] - spec.ubu) <= 1e-6)
+    print(f'ALT-a active set vs BVLS: {err:.2e}; {100 * on.mean():.0f} % on a bound, {o["fallback"].sum()} handed over')
+    assert err < 1e-9
+    assert on.mean() >= 0.10 and o['fallback'].any()
+    assert (o['U'] >= spec.lbu - 1e-9).all() and (o['U'] <= spec.ubu + 1e-9).all()
