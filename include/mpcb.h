@@ -198,6 +198,45 @@ int mpcb_eval(mpcb_handle* h, int64_t B,
               void* hip_stream);
 
 /*
+ * Vector-Jacobian product of one mpcb_solve_iterate step (12/4 model, both dtypes, with and
+ * without the input box).  Let J be the Jacobian of (X, U) with respect to (x0, xref, uref), taken
+ * at fixed xbar, ubar, wind, weights, model and active set; the outputs are J^T (gX, gU):
+ *   xbar [B,N+1,nx], ubar [B,N,nu]   the linearisation point the solve was given (xbar_N is not read)
+ *   U    [B,N,nu]                    the solve's output, read only for the active set; NULL allowed
+ *                                    iff the handle has no input box
+ *   gX [B,N+1,nx], gU [B,N,nu]       cotangents of X and U; either may be NULL (= 0), not both.  A
+ *                                    cotangent of u0 is added to gU[:, 0] by the caller
+ *   gx0 [B,nx], gxref [B,N+1,nx], guref [B,N,nu]   the gradients; any may be NULL, not all.  For a
+ *                                    broadcast reference (stride 0 in the solve) the caller sums over B
+ * All arrays are contiguous.  In iterate mode the linearisation point does not depend on the
+ * differentiated inputs, so (X, U) is affine in them on each active set and the product is exact:
+ * one more LQ solve over the same [A_k | B_k] with linear terms (-gX, -gU), no gaps and dx_0 = 0.
+ * xbar and ubar are treated as constants (Gauss-Newton / RTI): no gradient with respect to them,
+ * the weights, the model or wind is offered.  Rollout mode is not covered: there the linearisation
+ * point depends on x0.
+ * Active set: component (k, m) is clamped iff U[k,m] <= lbu[m] or U[k,m] >= ubu[m], compared in
+ * the handle's dtype (the box kernels write the bound value itself into clamped components, so a
+ * solve's own U gives its final set).  Clamped components have zero sensitivity.  At a degenerate
+ * point (clamped with a zero multiplier) this is one of the valid one-sided derivatives.  An
+ * instance that the active set handed to the interior point (mpcb_config.max_as_iter) returns U
+ * inside the box, within that method's tolerance of the bounds and not on them: its clamped
+ * components are not recognised and its product is the unconstrained one.
+ * status[B]: MPCB_STATUS_OK; MPCB_STATUS_NAN for an instance with a non-finite input or cotangent
+ * (its outputs are all NaN, other instances are unaffected); MPCB_STATUS_QP_FAIL when the masked
+ * input Hessian of a stage is not positive definite.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle.  The workspace of this call is allocated by the first call
+ * on the handle and is not part of what the handle's workspace size reports.
+ * No reference counterpart (acados offers solution sensitivities through a separate solver build).
+ */
+int mpcb_solve_vjp(mpcb_handle* h, int64_t B,
+                   const void* xbar, const void* ubar,
+                   const void* U,
+                   const void* wind, int64_t wind_sb,
+                   const void* gX, const void* gU,
+                   void* gx0, void* gxref, void* guref,
+                   int32_t* status, void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */

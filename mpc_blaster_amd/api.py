@@ -199,6 +199,44 @@ class BatchedMPC:
             self._ptr(out['res_ineq']), self._ptr(out.get('res_stat')), self._stream()))
         return out
 
+    def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None):
+        """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 12/4 model): with J the
+        Jacobian of (X, U) with respect to (x0, x_ref, u_ref) at fixed xbar, ubar, wind, weights
+        and active set, returns J^T (gX, gU) as a dict of device tensors ``gx0`` [B,12],
+        ``gxref`` [B,N+1,12], ``guref`` [B,N,4] and ``status`` [B] (int32).  ``gX`` [B,N+1,12] and
+        ``gU`` [B,N,4] are the cotangents (one may be None = 0; add a cotangent of u0 to
+        ``gU[:, 0]``).  ``U`` [B,N,4] is the solve's output, read for the active set: required on
+        an input-box handle.  Per-instance gradients: sum ``gxref`` / ``guref`` over the batch for
+        a reference that was broadcast.  Asynchronous, like ``evaluate``."""
+        torch = _torch()
+        N = self.cfg.N
+        xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar')
+        B = xb.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        ub, _ = self._dev(ubar, (N, self.nu), 'ubar', B)
+        gXd = None if gX is None else self._dev(gX, (N + 1, self.nx), 'gX', B)[0]
+        gUd = None if gU is None else self._dev(gU, (N, self.nu), 'gU', B)[0]
+        Ud = None if U is None else self._dev(U, (N, self.nu), 'U', B)[0]
+        wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
+        dev = self._tdev
+        out = dict(gx0=torch.empty((B, self.nx), dtype=self.dtype, device=dev),
+                   gxref=torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev),
+                   guref=torch.empty((B, N, self.nu), dtype=self.dtype, device=dev),
+                   status=torch.empty((B,), dtype=torch.int32, device=dev))
+        self._keep_vjp = (xb, ub, gXd, gUd, Ud, wd)
+        _lib.check(self.lib.mpcb_solve_vjp(
+            self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Ud), self._ptr(wd), wd_sb,
+            self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']), self._ptr(out['gxref']),
+            self._ptr(out['guref']), self._ptr(out['status']), self._stream()))
+        return out
+
+    def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None):
+        """``solve_iterate`` as a differentiable torch operation: returns (u0, X, U) whose
+        gradients flow to ``x0``, ``x_ref`` and ``u_ref`` (see ``mpc_blaster_amd.autograd``)."""
+        from .autograd import solve_iterate_diff
+        return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind)
+
     def set_params(self, p):
         """Parameters of the full 17/6 model (acados ``set(k, 'p', p)``,
         simulation_blaster.py:65-69): column-major J_angles 3x2, J_euler 3x3, J_p 3x3, T_blast.

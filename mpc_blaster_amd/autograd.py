@@ -1,0 +1,85 @@
+"""The SQP_RTI step as a differentiable torch operation.
+
+``solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None) -> (u0, X, U)`` runs
+``BatchedMPC.solve_iterate`` in the forward pass and one ``mpcb_solve_vjp`` call
+(include/mpcb.h) in the backward pass, so a loss on ``u0``, ``X``, ``U`` can be differentiated with
+respect to ``x0``, ``x_ref`` and ``u_ref``.
+
+What the gradient is.  In iterate mode the linearisation point (xbar, ubar) does not depend on the
+differentiated inputs, so (X, U) is affine in them, piecewise affine with the input box, and the
+gradient is exact on the active set of the forward solve (at a degenerate point, a clamped
+component with a zero multiplier, it is one of the valid one-sided derivatives).  The active set
+is read from U (a component on a bound is clamped): an instance the solver handed to its interior
+point has U strictly inside the box and gets the unconstrained gradient (include/mpcb.h).  ``xbar``,
+``ubar`` and ``wind`` are constants (Gauss-Newton / RTI): their gradients are ``None``, as are those
+of the weights and the model.  An instance whose forward status is not 0 gets zero gradients.  A
+reference passed as one row (``[1, ...]`` or without a batch axis) receives the sum of the
+per-instance gradients.  12/4 model only; not differentiable twice.
+
+torch is imported on first use, as in ``api.py``.
+"""
+from __future__ import annotations
+
+_FN = None
+
+
+def _function():
+    global _FN
+    if _FN is not None:
+        return _FN
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolveIterate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind):
+            N = mpc.cfg.N
+            x0d, _ = mpc._dev(x0.detach(), (mpc.nx,), 'x0')
+            B = x0d.shape[0]
+            xb, _ = mpc._dev(xbar.detach() if torch.is_tensor(xbar) else xbar, (N + 1, mpc.nx), 'xbar', B)
+            ub, _ = mpc._dev(ubar.detach() if torch.is_tensor(ubar) else ubar, (N, mpc.nu), 'ubar', B)
+            wd = None
+            if wind is not None:
+                wd, _ = mpc._dev(wind.detach() if torch.is_tensor(wind) else wind, (3,), 'wind', B,
+                                 allow_broadcast=True)
+            u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd)   # fresh outputs
+            X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
+            ctx.mpc = mpc
+            ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
+            ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
+            ctx.has_wind = wd is not None
+            ctx.save_for_backward(xb, ub, U, status, *((wd,) if wd is not None else ()))
+            return u0, X, U
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_u0, g_X, g_U):
+            mpc = ctx.mpc
+            xb, ub, U, status = ctx.saved_tensors[:4]
+            wd = ctx.saved_tensors[4] if ctx.has_wind else None
+            gU = g_U.to(mpc.dtype).clone()
+            gU[:, 0] += g_u0.to(mpc.dtype)
+            out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd)
+            ok = status == 0
+            grads = []
+            for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
+                g = torch.where(ok.reshape(-1, *([1] * (g.dim() - 1))), g, torch.zeros_like(g))
+                if len(shape) < g.dim() or shape[0] != g.shape[0]:
+                    g = g.sum(dim=0, keepdim=True)   # one row for the whole batch
+                grads.append(g.reshape(shape).to(dt))
+            need = ctx.needs_input_grad
+            return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
+                    grads[2] if need[5] else None, None)
+
+    _FN = SolveIterate
+    return _FN
+
+
+def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None):
+    """(u0 [B,4], X [B,N+1,12], U [B,N,4]) of ``mpc.solve_iterate``, differentiable with respect to
+    the torch tensors ``x0``, ``x_ref`` and ``u_ref`` (module docstring).  The per-instance status
+    is ``mpc.get_status()``."""
+    import torch
+    x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
+                        for t in (x0, x_ref, u_ref))
+    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind)

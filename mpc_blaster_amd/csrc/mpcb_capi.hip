@@ -14,6 +14,7 @@
 #include "../../include/mpcb.h"
 #include "mpcb_full.h"
 #include "mpcb_kernels.h"
+#include "mpcb_vjp.h"
 
 using namespace mpcb;
 
@@ -98,6 +99,9 @@ struct mpcb_handle {
   void* u_scratch = nullptr;     // fp32 12/4 input box: U when the caller passes none (the
                                  // refinement kernel restarts from the active set's U, mpcb_as.h)
   const void* last_fn[LOG_SLOTS] = {};   // kernels the last solve launched (mpcb_last_kernels)
+  void* vjp_scratch = nullptr;   // mpcb_solve_vjp's slot workspace: allocated by its first call, not
+                                 // counted in scratch_bytes
+  int vjp_grid = 0;              // ... and its resident slots
 };
 
 // A 17/6 call over B instances may only read parameter rows that exist (mpcb_set_params count).
@@ -487,6 +491,7 @@ extern "C" int mpcb_destroy(mpcb_handle* h) {
   (void)hipFree(h->weights);
   if (h->qp_stats) (void)hipFree(h->qp_stats);
   if (h->u_scratch) (void)hipFree(h->u_scratch);
+  if (h->vjp_scratch) (void)hipFree(h->vjp_scratch);
   delete h;
   return MPCB_OK;
 }
@@ -897,6 +902,70 @@ extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_s
                              res_ineq, res_stat, stream);
   return eval_impl<float>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, cost, res_eq,
                           res_ineq, res_stat, stream);
+}
+
+template <class T>
+static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                    const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
+                    void* gxref, void* guref, int32_t* status, void* stream) {
+  const int64_t slot = vjp_slot_elems(h->cfg.N);
+  if (!h->vjp_scratch) {
+    // resident slots: at most 8 one-wave workgroups per CU fit (registers: <= 2 waves per SIMD)
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    int64_t grid = (int64_t)cus * 8;
+    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
+    // MPCB_VJP_SLOTS: fewer slots, so that a small batch strides over them (tests)
+    if (const char* e = getenv("MPCB_VJP_SLOTS"))
+      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
+    if (grid > waves) grid = waves;
+    if (grid < 1) grid = 1;
+    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
+    const hipError_t e = hipMalloc(&h->vjp_scratch, bytes);
+    if (e != hipSuccess) {
+      h->vjp_scratch = nullptr;
+      return fail(MPCB_E_NOMEM, "vjp workspace %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    h->vjp_grid = (int)grid;
+  }
+  VjpArgs<T> a;
+  a.B = B;
+  a.N = h->cfg.N;
+  a.box = h->cfg.box_u;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = (const Weights<T>*)h->weights;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar; a.U = (const T*)U;
+  a.wind = (const T*)wind; a.wind_sb = wind_sb;
+  a.gX = (const T*)gX; a.gU = (const T*)gU;
+  a.gx0 = (T*)gx0; a.gxref = (T*)gxref; a.guref = (T*)guref;
+  a.status = status;
+  a.scratch = (T*)h->vjp_scratch;
+  a.slot_elems = slot;
+  int64_t grid = (B + GROUPS - 1) / GROUPS;
+  if (grid > h->vjp_grid) grid = h->vjp_grid;
+  const hipError_t e = launch_vjp<T>(a, (int)grid, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "vjp launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_vjp(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                              const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
+                              void* gxref, void* guref, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product covers the 12/4 model only");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (h->cfg.box_u && !U) return fail(MPCB_E_INVALID, "U is required on an input-box handle (the active set)");
+  if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
+  if (!gx0 && !gxref && !guref) return fail(MPCB_E_INVALID, "no output requested");
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->cfg.dtype == MPCB_F64)
+    return vjp_impl<double>(h, B, xbar, ubar, U, wind, wind_sb, gX, gU, gx0, gxref, guref, status, stream);
+  return vjp_impl<float>(h, B, xbar, ubar, U, wind, wind_sb, gX, gU, gx0, gxref, guref, status, stream);
 }
 
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,

@@ -1,0 +1,34 @@
+// mpcb_vjp.h — launch interface of the SQP_RTI step's vector-Jacobian product (mpcb_vjp.hip;
+// mpcb_solve_vjp in include/mpcb.h).  Internal to the library.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mpcb_kernels.h"
+
+namespace mpcb {
+
+template <class T>
+struct VjpArgs {
+  int64_t B;
+  int N;
+  int box;                           // input box on: the active set is read from U
+  T h, s;                            // RK4 step, stage cost scaling
+  Model<T> M;
+  const Weights<T>* W;
+  const T* xbar; const T* ubar;      // [B, N+1, nx], [B, N, nu]: the linearisation point
+  const T* U;                        // [B, N, nu], nullable without the box
+  const T* wind; int64_t wind_sb;    // nullable
+  const T* gX; const T* gU;          // cotangents, either nullable
+  T* gx0; T* gxref; T* guref;        // [B, nx], [B, N+1, nx], [B, N, nu], each nullable
+  int32_t* status;
+  T* scratch;                        // per-slot workspace (one slot = one wavefront = GROUPS instances)
+  int64_t slot_elems;
+};
+
+// elements of one workspace slot: the captured linearisation scalars and the gains of N stages
+int64_t vjp_slot_elems(int N);
+// grid: resident slots (the kernel strides over the waves of the batch)
+template <class T> hipError_t launch_vjp(const VjpArgs<T>& a, int grid, hipStream_t st);
+
+}  // namespace mpcb

@@ -1,0 +1,127 @@
+#!/usr/bin/env python
+"""Device time of mpcb_solve_vjp next to mpcb_solve_iterate at the same shape.
+
+The backward pass of the torch layer (mpc_blaster_amd/autograd.py) is one mpcb_solve_vjp call, the
+forward pass one mpcb_solve_iterate call, so their ratio is what a gradient costs on top of a
+solve.  The product runs the pass structure of the single-kernel solver (mpcb_solve.hip: nominal,
+backward Riccati, forward, one launch), so that path (a handle created under
+MPCB_SPLIT_MIN_BATCH above the batch; MPCB_BOX_IMPL=v1 with the box) is timed as well, next to the
+default path of the handle.  Shapes: c2 (4096 x N = 20, fp64), c3 (65536 x N = 20, fp32, sine
+references) and one 65536-instance shard of c4 (N = 30, fp32, input box [0, 65]).
+
+The iterate is one rollout-mode RTI step; U of the timed solve_iterate gives the product's active
+set; the cotangents are standard normal.  HIP events around ``--inner`` back-to-back calls, median
+of ``--runs`` after ``--warmup`` calls of every variant, the variants alternating so drift hits
+them alike.  Prints one JSON line per shape.
+
+    python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPES = {
+    # name: (B, N, dtype, references, box, seed)
+    'c2': (4096, 20, 'f64', 'hover', False, 1002),
+    'c3': (65536, 20, 'f32', 'sine', False, 1003),
+    'c4': (65536, 30, 'f32', 'hover', True, 1004),
+}
+
+
+def _handle(N, dtype, box, B, env):
+    import numpy as np
+
+    from mpc_blaster_amd import BatchedMPC, MPCConfig
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return BatchedMPC(MPCConfig(N=N, dtype=dtype, lbu=np.zeros(4) if box else None,
+                                    ubu=np.full(4, 65.0) if box else None), max_batch=B)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def bench(name, runs, warmup, inner):
+    import torch
+
+    from mpc_blaster_amd import _lib
+    B, N, dtype, ref, box, seed = SHAPES[name]
+    m = _handle(N, dtype, box, B, {})
+    single_env = {'MPCB_BOX_IMPL': 'v1'} if box else {'MPCB_SPLIT_MIN_BATCH': str(1 << 40)}
+    ms1 = _handle(N, dtype, box, B, single_env)
+    assert ms1.path == 'fused' and (box or m.path == 'split')
+    inp = m.gen_inputs(B, seed=seed, ref=ref, wind=False)
+    m.solve(inp['x0'], inp['xref'], inp['uref'])
+    xbar, ubar = m.get_state_trajectory().clone(), m.get_input_trajectory().clone()
+    x0, xr, ur = inp['x0'], inp['xref'], inp['uref']
+    xr_sb = (N + 1) * 12 if ref == 'sine' else 0
+    dev, dt = xbar.device, xbar.dtype
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    gX = torch.randn((B, N + 1, 12), dtype=dt, device=dev, generator=gen)
+    gU = torch.randn((B, N, 4), dtype=dt, device=dev, generator=gen)
+    u0 = torch.empty((B, 4), dtype=dt, device=dev)
+    X, U = torch.empty_like(xbar), torch.empty_like(ubar)
+    gx0, gxr, gur = torch.empty((B, 12), dtype=dt, device=dev), torch.empty_like(xbar), torch.empty_like(ubar)
+    st_s = torch.empty((B,), dtype=torch.int32, device=dev)
+    st_v = torch.empty((B,), dtype=torch.int32, device=dev)
+    P, null, st = m._ptr, m._ptr(None), m._stream()
+
+    # (the single-kernel solver gets outputs of its own: the product reads the default path's U)
+    o1 = (torch.empty_like(u0), torch.empty_like(X), torch.empty_like(U), torch.empty_like(st_s))
+
+    def solve_call(hd, o):
+        return lambda: _lib.check(hd.lib.mpcb_solve_iterate(hd._h, B, P(x0), 12, P(xbar), P(ubar), P(xr), xr_sb,
+                                                            P(ur), 0, null, 0, P(o[0]), P(o[1]), P(o[2]), P(o[3]), st))
+    variants = {
+        'solve_iterate': solve_call(m, (u0, X, U, st_s)),
+        'solve_iterate_single': solve_call(ms1, o1),
+        'vjp': lambda: _lib.check(m.lib.mpcb_solve_vjp(m._h, B, P(xbar), P(ubar), P(U) if box else null, null, 0,
+                                                       P(gX), P(gU), P(gx0), P(gxr), P(gur), P(st_v), st)),
+    }
+    for _ in range(warmup):
+        for f in variants.values():
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(runs):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) / inner)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = dict(shape=name, B=B, N=N, dtype=dtype, box=box, runs=runs, inner=inner,
+               **{f'{k}_ms': round(v, 4) for k, v in med.items()},
+               **{f'{k}_min_ms': round(min(v), 4) for k, v in t.items()},
+               vjp_over_solve=round(med['vjp'] / med['solve_iterate'], 3),
+               vjp_over_single=round(med['vjp'] / med['solve_iterate_single'], 3),
+               solve_status_ok=int((st_s == 0).sum()), vjp_status_ok=int((st_v == 0).sum()),
+               clamped_fraction=(float(((U <= 0.0) | (U >= 65.0)).double().mean()) if box else 0.0))
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--runs', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--inner', type=int, default=5, help='launches per event pair')
+    ap.add_argument('--shapes', default='c2,c3,c4')
+    a = ap.parse_args()
+    for name in a.shapes.split(','):
+        bench(name, a.runs, a.warmup, a.inner)
+
+
+if __name__ == '__main__':
+    main()
