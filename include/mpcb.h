@@ -212,8 +212,8 @@ int mpcb_eval(mpcb_handle* h, int64_t B,
  * differentiated inputs, so (X, U) is affine in them on each active set and the product is exact:
  * one more LQ solve over the same [A_k | B_k] with linear terms (-gX, -gU), no gaps and dx_0 = 0.
  * xbar and ubar are treated as constants (Gauss-Newton / RTI): no gradient with respect to them,
- * the weights, the model or wind is offered.  Rollout mode is not covered: there the linearisation
- * point depends on x0.
+ * the model or wind is offered (the cost weights: mpcb_solve_vjp_w below).  Rollout mode is not
+ * covered: there the linearisation point depends on x0.
  * Active set: component (k, m) is clamped iff U[k,m] <= lbu[m] or U[k,m] >= ubu[m], compared in
  * the handle's dtype (the box kernels write the bound value itself into clamped components, so a
  * solve's own U gives its final set).  Clamped components have zero sensitivity.  At a degenerate
@@ -235,6 +235,43 @@ int mpcb_solve_vjp(mpcb_handle* h, int64_t B,
                    const void* gX, const void* gU,
                    void* gx0, void* gxref, void* guref,
                    int32_t* status, void* hip_stream);
+
+/*
+ * mpcb_solve_vjp plus the gradients with respect to the cost weights, in the same launch.  With
+ * L = <gX, X> + <gU, U> and (dx, du) the adjoint step of mpcb_solve_vjp (the solution that gives
+ * gxref_k = s Q dx_k; du = 0 on clamped components, dx_0 = 0), at a fixed linearisation point and
+ * active set
+ *   rx_k = X_k - xref_k,  ru_k = U_k - uref_k      (X, U: what mpcb_solve_iterate returned)
+ *   gQ  = -s sym(sum_{k<N} dx_k rx_k^T)   [B,nx,nx]
+ *   gR  = -s sym(sum_{k<N} du_k ru_k^T)   [B,nu,nu]
+ *   gQN =   -sym(dx_N rx_N^T)             [B,nx,nx]     sym(M) = (M + M^T) / 2,  s = cfg.cost_scale
+ * row-major, of the handle's dtype, per instance (the weights are shared by the batch: the caller
+ * sums over B; the kernel uses no atomics, so results are bit-reproducible) and bitwise symmetric.
+ * Convention: the weights are symmetric matrices, so for any symmetric perturbation dQ of Q the
+ * change of L is <gQ, dQ>_F (likewise R, QN); the derivative with respect to a diagonal entry is
+ * gQ[i][i], with respect to the pair of entries (i, j) and (j, i) moved together 2 gQ[i][j].
+ * Exact on the active set, like the product itself (L is not affine in the weights).
+ *   X [B,N+1,nx], U [B,N,nu], xref / uref with the solve's strides (0 = broadcast): required iff
+ *   one of gQ, gR, gQN is given; otherwise the rules of mpcb_solve_vjp hold (X, xref and uref are
+ *   not read, U is required on an input-box handle only)
+ *   any of the six outputs may be NULL, not all
+ * A call without a weight output launches the kernels of mpcb_solve_vjp and returns its bits.
+ * Inherited limit: an instance that the active set handed to the interior point has U inside the
+ * box, so its clamped components are not recognised and its gradients are the unconstrained ones.
+ * X, U, xref and uref join the NaN rule: a non-finite entry gives that instance status
+ * MPCB_STATUS_NAN and NaN in all six outputs.  MPCB_E_UNSUPPORTED on a 17/6 handle, MPCB_E_INVALID
+ * for a missing argument.
+ */
+int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B,
+                     const void* xbar, const void* ubar,
+                     const void* X, const void* U,
+                     const void* xref, int64_t xref_sb,
+                     const void* uref, int64_t uref_sb,
+                     const void* wind, int64_t wind_sb,
+                     const void* gX, const void* gU,
+                     void* gx0, void* gxref, void* guref,
+                     void* gQ, void* gR, void* gQN,
+                     int32_t* status, void* hip_stream);
 
 /*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
@@ -277,6 +314,20 @@ int mpcb_set_params(mpcb_handle* h, int64_t count, const void* params, int64_t p
  * device (a configuration call, not a per-step one).
  */
 int mpcb_set_t_blast(mpcb_handle* h, double t_blast);
+
+/*
+ * New cost weights for an existing handle: replaces acados ``cost_set(k, 'W', W)`` for a W that is
+ * the same on all stages 0..N-1 (Q = W[:nx,:nx], R = W[nx:,nx:]) plus the terminal ``W_e`` (QN); no
+ * re-creation of the handle or its workspace.  Q, R, QN are HOST arrays, row-major nx x nx, nu x nu
+ * and nx x nx; NULL keeps the current matrix.  Every entry must be finite and each matrix symmetric
+ * by the rule of mpcb_config; otherwise MPCB_E_INVALID and the handle is unchanged.  Updates the
+ * handle's config and refills and uploads its whole weights block (every table derived from the
+ * weights), on both models and every kernel path.  Waits for the device (a configuration call,
+ * like mpcb_set_t_blast).  After any sequence of mpcb_set_t_blast, mpcb_set_params and
+ * mpcb_set_weights calls the handle computes, bit for bit, what a handle created with the final
+ * values computes.
+ */
+int mpcb_set_weights(mpcb_handle* h, const double* Q, const double* R, const double* QN);
 
 /*
  * Point-of-contact Jacobians of the blaster stream for B vehicle poses (fp64, runs on the

@@ -21,7 +21,8 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
            'mpcb_workspace_bytes', 'mpcb_path', 'mpcb_solve', 'mpcb_solve_iterate', 'mpcb_linearize',
            'mpcb_sim_step', 'mpcb_gen_inputs', 'mpcb_histogram', 'mpcb_set_timing',
            'mpcb_last_timing', 'mpcb_set_params', 'mpcb_set_t_blast', 'mpcb_qp_stats', 'mpcb_poc_jacobians',
-           'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp')
+           'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp',
+           'mpcb_solve_vjp_w', 'mpcb_set_weights')
 # the timing / launch-log slots of the split path (mpcb_last_timing, mpcb_plan_kernels) and of the
 # 17/6 model
 PHASES_12 = ('nominal', 'riccati', 'forward', 'linearise')
@@ -81,6 +82,9 @@ def load(path: str | None = None):
     lib.mpcb_linearize.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.mpcb_eval.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp]
     lib.mpcb_solve_vjp.argtypes = [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.mpcb_solve_vjp_w.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp,
+                                     vp, vp, vp, vp, vp]
+    lib.mpcb_set_weights.argtypes = [vp, ctypes.POINTER(dbl), ctypes.POINTER(dbl), ctypes.POINTER(dbl)]
     lib.mpcb_sim_step.argtypes =[vp, i64, vp, vp, vp, i64, dbl, vp, vp]
     lib.mpcb_gen_inputs.argtypes = [vp, i64, u64, u64, i32, vp, vp, i64, vp, i64, vp, vp]
     lib.mpcb_histogram.argtypes = [vp, i64, vp, dbl, dbl, i32, vp, vp]

@@ -44,6 +44,7 @@ class BatchedMPC:
         self.nx, self.nu = config.nx, config.nu
         self._u0 = self._X = self._U = self._status = None
         self._params = None
+        self._weights_version = 0   # bumped by set_weights (autograd checks it in backward)
 
     # ------------------------------------------------------------------ helpers
     def close(self):
@@ -199,7 +200,8 @@ class BatchedMPC:
             self._ptr(out['res_ineq']), self._ptr(out.get('res_stat')), self._stream()))
         return out
 
-    def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None):
+    def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None, X=None, x_ref=None,
+                          u_ref=None, weights=False):
         """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 12/4 model): with J the
         Jacobian of (X, U) with respect to (x0, x_ref, u_ref) at fixed xbar, ubar, wind, weights
         and active set, returns J^T (gX, gU) as a dict of device tensors ``gx0`` [B,12],
@@ -207,7 +209,13 @@ class BatchedMPC:
         ``gU`` [B,N,4] are the cotangents (one may be None = 0; add a cotangent of u0 to
         ``gU[:, 0]``).  ``U`` [B,N,4] is the solve's output, read for the active set: required on
         an input-box handle.  Per-instance gradients: sum ``gxref`` / ``guref`` over the batch for
-        a reference that was broadcast.  Asynchronous, like ``evaluate``."""
+        a reference that was broadcast.  Asynchronous, like ``evaluate``.
+
+        ``weights=True`` (mpcb_solve_vjp_w, the same launch) adds the gradients with respect to
+        the cost weights, per instance: ``gQ`` [B,12,12], ``gR`` [B,4,4], ``gQN`` [B,12,12],
+        symmetric; for a symmetric perturbation dQ the loss changes by <gQ.sum(0), dQ>.  It needs
+        the solve's output ``X`` [B,N+1,12] and ``U`` and its references ``x_ref`` [B|1,N+1,12],
+        ``u_ref`` [B|1,N,4] (include/mpcb.h has the formula)."""
         torch = _torch()
         N = self.cfg.N
         xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar')
@@ -224,6 +232,22 @@ class BatchedMPC:
                    gxref=torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev),
                    guref=torch.empty((B, N, self.nu), dtype=self.dtype, device=dev),
                    status=torch.empty((B,), dtype=torch.int32, device=dev))
+        if weights:
+            if X is None or U is None or x_ref is None or u_ref is None:
+                raise ValueError('weights=True needs X, U, x_ref and u_ref of the solve')
+            Xd, _ = self._dev(X, (N + 1, self.nx), 'X', B)
+            xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
+            ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
+            out.update(gQ=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev),
+                       gR=torch.empty((B, self.nu, self.nu), dtype=self.dtype, device=dev),
+                       gQN=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev))
+            self._keep_vjp = (xb, ub, gXd, gUd, Ud, wd, Xd, xr, ur)
+            _lib.check(self.lib.mpcb_solve_vjp_w(
+                self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Xd), self._ptr(Ud), self._ptr(xr), xr_sb,
+                self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(gXd), self._ptr(gUd),
+                self._ptr(out['gx0']), self._ptr(out['gxref']), self._ptr(out['guref']), self._ptr(out['gQ']),
+                self._ptr(out['gR']), self._ptr(out['gQN']), self._ptr(out['status']), self._stream()))
+            return out
         self._keep_vjp = (xb, ub, gXd, gUd, Ud, wd)
         _lib.check(self.lib.mpcb_solve_vjp(
             self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Ud), self._ptr(wd), wd_sb,
@@ -231,11 +255,42 @@ class BatchedMPC:
             self._ptr(out['guref']), self._ptr(out['status']), self._stream()))
         return out
 
-    def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None):
+    def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None):
         """``solve_iterate`` as a differentiable torch operation: returns (u0, X, U) whose
-        gradients flow to ``x0``, ``x_ref`` and ``u_ref`` (see ``mpc_blaster_amd.autograd``)."""
+        gradients flow to ``x0``, ``x_ref`` and ``u_ref`` and, when given, to the weight tensors
+        ``Q``, ``R``, ``QN``, which the forward pass installs with ``set_weights`` (see
+        ``mpc_blaster_amd.autograd``)."""
         from .autograd import solve_iterate_diff
-        return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind)
+        return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN)
+
+    def set_weights(self, Q=None, R=None, QN=None):
+        """New cost weights on this handle (mpcb_set_weights; acados ``cost_set(k, 'W', W)`` with
+        the same W on every stage, and ``W_e``): no re-creation of the handle or its workspace.
+        Each of ``Q`` [12] or [12,12], ``R`` [4] or [4,4], ``QN`` like Q (17 / 6 on the full
+        model) is a vector (the diagonal) or a symmetric matrix, NumPy or torch; None keeps the
+        current one.  The values are read on the host, so a device tensor costs a
+        synchronisation, and the call waits for the device: a configuration call like
+        ``set_t_blast``.  Afterwards the handle solves like one created with the new weights."""
+        mats = []
+        for name, w, n in (('Q', Q, self.nx), ('R', R, self.nu), ('QN', QN, self.nx)):
+            if w is None:
+                mats.append(None)
+                continue
+            if hasattr(w, 'detach'):
+                w = w.detach().cpu().numpy()
+            w = np.asarray(w, dtype=np.float64)
+            if w.shape == (n,):
+                w = np.diag(w)
+            if w.shape != (n, n):
+                raise ValueError(f'{name}: expected [{n}] or [{n}, {n}], got {w.shape}')
+            mats.append(np.ascontiguousarray(w))
+        dp = ctypes.POINTER(ctypes.c_double)
+        _lib.check(self.lib.mpcb_set_weights(self._h, *[None if m is None else m.ctypes.data_as(dp) for m in mats]))
+        for name, m in zip(('Q', 'R', 'QN'), mats):
+            if m is not None:
+                setattr(self.cfg, name, m.copy())
+        self._c = self.cfg.to_c()
+        self._weights_version += 1
 
     def set_params(self, p):
         """Parameters of the full 17/6 model (acados ``set(k, 'p', p)``,

@@ -1,9 +1,10 @@
 """The SQP_RTI step as a differentiable torch operation.
 
-``solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None) -> (u0, X, U)`` runs
-``BatchedMPC.solve_iterate`` in the forward pass and one ``mpcb_solve_vjp`` call
-(include/mpcb.h) in the backward pass, so a loss on ``u0``, ``X``, ``U`` can be differentiated with
-respect to ``x0``, ``x_ref`` and ``u_ref``.
+``solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None)
+-> (u0, X, U)`` runs ``BatchedMPC.solve_iterate`` in the forward pass and one ``mpcb_solve_vjp``
+call (``mpcb_solve_vjp_w`` when a weight gradient is needed; include/mpcb.h) in the backward pass,
+so a loss on ``u0``, ``X``, ``U`` can be differentiated with respect to ``x0``, ``x_ref``, ``u_ref``
+and the cost weights.
 
 What the gradient is.  In iterate mode the linearisation point (xbar, ubar) does not depend on the
 differentiated inputs, so (X, U) is affine in them, piecewise affine with the input box, and the
@@ -11,10 +12,22 @@ gradient is exact on the active set of the forward solve (at a degenerate point,
 component with a zero multiplier, it is one of the valid one-sided derivatives).  The active set
 is read from U (a component on a bound is clamped): an instance the solver handed to its interior
 point has U strictly inside the box and gets the unconstrained gradient (include/mpcb.h).  ``xbar``,
-``ubar`` and ``wind`` are constants (Gauss-Newton / RTI): their gradients are ``None``, as are those
-of the weights and the model.  An instance whose forward status is not 0 gets zero gradients.  A
+``ubar`` and ``wind`` are constants (Gauss-Newton / RTI): their gradients are ``None``, as is that
+of the model.  An instance whose forward status is not 0 gets zero gradients.  A
 reference passed as one row (``[1, ...]`` or without a batch axis) receives the sum of the
 per-instance gradients.  12/4 model only; not differentiable twice.
+
+The weights.  ``Q``, ``R``, ``QN`` are optional torch tensors: a vector (the diagonal) or a
+symmetric matrix.  The weights belong to the handle, so the forward pass installs the value of
+every weight tensor it is given with ``mpc.set_weights`` before it solves: that reads the tensor
+on the host (a synchronisation) and waits for the device, and the handle keeps the new weights
+afterwards.  The backward pass returns, for each weight tensor, the gradient summed over the
+instances with forward status 0, in the tensor's shape and dtype: the symmetric matrix gQ of
+include/mpcb.h for a matrix (so that dL = <gQ, dQ> for a symmetric dQ), its diagonal for a vector.
+It is exact on the active set at fixed (xbar, ubar), like the others.  The backward pass needs the
+weights the forward pass solved with: it raises ``RuntimeError`` if ``set_weights`` (or another
+forward pass with weight tensors) has changed the handle's weights in between.  Without weight
+arguments nothing of this applies and the layer is as before.
 
 torch is imported on first use, as in ``api.py``.
 """
@@ -32,7 +45,7 @@ def _function():
 
     class SolveIterate(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind):
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN):
             N = mpc.cfg.N
             x0d, _ = mpc._dev(x0.detach(), (mpc.nx,), 'x0')
             B = x0d.shape[0]
@@ -42,13 +55,22 @@ def _function():
             if wind is not None:
                 wd, _ = mpc._dev(wind.detach() if torch.is_tensor(wind) else wind, (3,), 'wind', B,
                                  allow_broadcast=True)
+            wts = (Q, R, QN)
+            ctx.has_weights = any(w is not None for w in wts)
+            if ctx.has_weights:
+                mpc.set_weights(*wts)
             u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd)   # fresh outputs
             X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
             ctx.mpc = mpc
             ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
             ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
             ctx.has_wind = wd is not None
-            ctx.save_for_backward(xb, ub, U, status, *((wd,) if wd is not None else ()))
+            saved = [xb, ub, U, status] + ([wd] if wd is not None else [])
+            if ctx.has_weights:
+                ctx.wmeta = [None if w is None else (tuple(w.shape), w.dtype) for w in wts]
+                ctx.wversion = mpc._weights_version
+                saved += [X, x_ref.detach(), u_ref.detach()]
+            ctx.save_for_backward(*saved)
             return u0, X, U
 
         @staticmethod
@@ -57,9 +79,20 @@ def _function():
             mpc = ctx.mpc
             xb, ub, U, status = ctx.saved_tensors[:4]
             wd = ctx.saved_tensors[4] if ctx.has_wind else None
+            need = ctx.needs_input_grad
+            want_w = ctx.has_weights and any(need[7:10])
             gU = g_U.to(mpc.dtype).clone()
             gU[:, 0] += g_u0.to(mpc.dtype)
-            out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd)
+            if want_w:
+                if mpc._weights_version != ctx.wversion:
+                    raise RuntimeError('the weights of the MPC handle changed after the forward pass '
+                                       '(set_weights or another forward with weight tensors): the '
+                                       'weight gradient needs the weights the forward solved with')
+                X, xr, ur = ctx.saved_tensors[-3:]
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd, X=X, x_ref=xr, u_ref=ur,
+                                            weights=True)
+            else:
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd)
             ok = status == 0
             grads = []
             for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
@@ -67,19 +100,27 @@ def _function():
                 if len(shape) < g.dim() or shape[0] != g.shape[0]:
                     g = g.sum(dim=0, keepdim=True)   # one row for the whole batch
                 grads.append(g.reshape(shape).to(dt))
-            need = ctx.needs_input_grad
+            wgrads = [None, None, None]
+            if want_w:
+                for i, key in enumerate(('gQ', 'gR', 'gQN')):
+                    if ctx.wmeta[i] is None or not need[7 + i]:
+                        continue
+                    shape, dt = ctx.wmeta[i]
+                    g = torch.where(ok.reshape(-1, 1, 1), out[key], torch.zeros_like(out[key])).sum(dim=0)
+                    wgrads[i] = (torch.diagonal(g) if len(shape) == 1 else g).reshape(shape).to(dt)
             return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
-                    grads[2] if need[5] else None, None)
+                    grads[2] if need[5] else None, None, *wgrads)
 
     _FN = SolveIterate
     return _FN
 
 
-def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None):
+def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None):
     """(u0 [B,4], X [B,N+1,12], U [B,N,4]) of ``mpc.solve_iterate``, differentiable with respect to
-    the torch tensors ``x0``, ``x_ref`` and ``u_ref`` (module docstring).  The per-instance status
-    is ``mpc.get_status()``."""
+    the torch tensors ``x0``, ``x_ref`` and ``u_ref`` and, when given, the weight tensors ``Q``, ``R``,
+    ``QN`` (vectors or symmetric matrices; installed on the handle by the forward pass, a host
+    synchronisation: module docstring).  The per-instance status is ``mpc.get_status()``."""
     import torch
     x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
                         for t in (x0, x_ref, u_ref))
-    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind)
+    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN)

@@ -399,6 +399,33 @@ static void select_path(mpcb_handle* h, const mpcb_config* cfg, int64_t max_batc
   h->scratch_bytes = h->chunk_elems * (int64_t)esz;
 }
 
+// The whole weights block of a handle (Weights<T>, or Weights17<T> on the 17/6 model) filled from
+// ``c`` and the handle's model, and uploaded: mpcb_create, and mpcb_set_weights with the handle's
+// current config (whose t_blast mpcb_set_t_blast keeps up to date) and the new weights.
+static hipError_t upload_weights(mpcb_handle* h, const mpcb_config& c) {
+  const bool f64 = c.dtype == MPCB_F64;
+  if (h->full && f64) {
+    Weights17<double> w;
+    fill_weights17(c, w);
+    return hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
+  }
+  if (h->full) {
+    Weights17<float> w;
+    fill_weights17(c, w);
+    return hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
+  }
+  if (f64) {
+    Weights<double> w;
+    fill_weights(c, w);
+    fill_row_table(h->Md, w.rowt);
+    return hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
+  }
+  Weights<float> w;
+  fill_weights(c, w);
+  fill_row_table(h->Mf, w.rowt);
+  return hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
+}
+
 // the fp32 refinement list's capacity: the whole batch (c4 lists 252 of 65,536, but on strongly
 // constrained draws most instances reach it through the interior-point fallback)
 static int64_t ref_cap(int64_t max_batch) { return max_batch; }
@@ -435,25 +462,7 @@ extern "C" int mpcb_create(const mpcb_config* cfg, int device, int64_t max_batch
     delete h;
     return fail(MPCB_E_NOMEM, "weights: %s", hipGetErrorString(e));
   }
-  if (full && f64) {
-    Weights17<double> w;
-    fill_weights17(*cfg, w);
-    e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
-  } else if (full) {
-    Weights17<float> w;
-    fill_weights17(*cfg, w);
-    e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
-  } else if (f64) {
-    Weights<double> w;
-    fill_weights(*cfg, w);
-    fill_row_table(h->Md, w.rowt);
-    e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
-  } else {
-    Weights<float> w;
-    fill_weights(*cfg, w);
-    fill_row_table(h->Mf, w.rowt);
-    e = hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
-  }
+  e = upload_weights(h, *cfg);
   if (e != hipSuccess) {
     (void)hipFree(h->scratch);
     (void)hipFree(h->weights);
@@ -905,9 +914,10 @@ extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_s
 }
 
 template <class T>
-static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* X, const void* U,
+                    const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
                     const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
-                    void* gxref, void* guref, int32_t* status, void* stream) {
+                    void* gxref, void* guref, void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
   const int64_t slot = vjp_slot_elems(h->cfg.N);
   if (!h->vjp_scratch) {
     // resident slots: at most 8 one-wave workgroups per CU fit (registers: <= 2 waves per SIMD)
@@ -940,6 +950,10 @@ static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* uba
   a.wind = (const T*)wind; a.wind_sb = wind_sb;
   a.gX = (const T*)gX; a.gU = (const T*)gU;
   a.gx0 = (T*)gx0; a.gxref = (T*)gxref; a.guref = (T*)guref;
+  a.X = (const T*)X;
+  a.xref = (const T*)xref; a.xref_sb = xref_sb;
+  a.uref = (const T*)uref; a.uref_sb = uref_sb;
+  a.gQ = (T*)gQ; a.gR = (T*)gR; a.gQN = (T*)gQN;
   a.status = status;
   a.scratch = (T*)h->vjp_scratch;
   a.slot_elems = slot;
@@ -950,22 +964,38 @@ static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* uba
   return MPCB_OK;
 }
 
-extern "C" int mpcb_solve_vjp(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
-                              const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
-                              void* gxref, void* guref, int32_t* status, void* stream) {
+extern "C" int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* X,
+                                const void* U, const void* xref, int64_t xref_sb, const void* uref,
+                                int64_t uref_sb, const void* wind, int64_t wind_sb, const void* gX,
+                                const void* gU, void* gx0, void* gxref, void* guref, void* gQ, void* gR,
+                                void* gQN, int32_t* status, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (h->full) return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product covers the 12/4 model only");
   if (B < 0 || B > h->max_batch)
     return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  const bool wg = gQ || gR || gQN;
   if (h->cfg.box_u && !U) return fail(MPCB_E_INVALID, "U is required on an input-box handle (the active set)");
   if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
-  if (!gx0 && !gxref && !guref) return fail(MPCB_E_INVALID, "no output requested");
+  if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
   if (B == 0) return MPCB_OK;
   if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (wg && (!X || !U || !xref || !uref))
+    return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
+  if (wg && (xref_sb < 0 || uref_sb < 0)) return fail(MPCB_E_INVALID, "negative reference stride");
   HIP_TRY(hipSetDevice(h->device));
   if (h->cfg.dtype == MPCB_F64)
-    return vjp_impl<double>(h, B, xbar, ubar, U, wind, wind_sb, gX, gU, gx0, gxref, guref, status, stream);
-  return vjp_impl<float>(h, B, xbar, ubar, U, wind, wind_sb, gX, gU, gx0, gxref, guref, status, stream);
+    return vjp_impl<double>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
+                            gxref, guref, gQ, gR, gQN, status, stream);
+  return vjp_impl<float>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
+                         gxref, guref, gQ, gR, gQN, status, stream);
+}
+
+// no weight output: the plain kernels, which read neither X nor the references
+extern "C" int mpcb_solve_vjp(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                              const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
+                              void* gxref, void* guref, int32_t* status, void* stream) {
+  return mpcb_solve_vjp_w(h, B, xbar, ubar, nullptr, U, nullptr, 0, nullptr, 0, wind, wind_sb, gX, gU, gx0,
+                          gxref, guref, nullptr, nullptr, nullptr, status, stream);
 }
 
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
@@ -1083,5 +1113,29 @@ extern "C" int mpcb_set_t_blast(mpcb_handle* h, double t_blast) {
                         sizeof(v), hipMemcpyHostToDevice));
     }
   }
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_set_weights(mpcb_handle* h, const double* Q, const double* R, const double* QN) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  mpcb_config c = h->cfg;   // nothing of the handle changes unless every check passes
+  const int nx = c.nx, nu = c.nu;
+  struct { const char* name; const double* src; double* dst; int n; } const wts[3] = {
+      {"Q", Q, c.Q, nx}, {"R", R, c.R, nu}, {"QN", QN, c.QN, nx}};
+  for (const auto& w : wts) {
+    if (!w.src) continue;
+    for (int i = 0; i < w.n * w.n; ++i) {
+      if (!std::isfinite(w.src[i]))
+        return fail(MPCB_E_INVALID, "%s[%d][%d] is not finite", w.name, i / w.n, i % w.n);
+      w.dst[i] = w.src[i];
+    }
+  }
+  double Jinv[9];
+  if (int rc = validate_config(&c, h->max_batch, Jinv)) return rc;   // the symmetry rule of mpcb_create
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());   // kernels in flight may still read the old block
+  const hipError_t e = upload_weights(h, c);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "weights upload: %s", hipGetErrorString(e));
+  h->cfg = c;
   return MPCB_OK;
 }

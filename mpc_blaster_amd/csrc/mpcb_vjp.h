@@ -1,5 +1,5 @@
 // mpcb_vjp.h — launch interface of the SQP_RTI step's vector-Jacobian product (mpcb_vjp.hip;
-// mpcb_solve_vjp in include/mpcb.h).  Internal to the library.
+// mpcb_solve_vjp and mpcb_solve_vjp_w in include/mpcb.h).  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,6 +24,12 @@ struct VjpArgs {
   int32_t* status;
   T* scratch;                        // per-slot workspace (one slot = one wavefront = GROUPS instances)
   int64_t slot_elems;
+  // weight gradients (mpcb_solve_vjp_w): any of gQ, gR, gQN non-null selects the kernel variant that
+  // forms them, which reads the solve's output and its references (all four required then)
+  const T* X;                        // [B, N+1, nx]; U above is then required without the box too
+  const T* xref; int64_t xref_sb;    // the solve's references and per-instance strides (0 = broadcast)
+  const T* uref; int64_t uref_sb;
+  T* gQ; T* gR; T* gQN;              // [B, nx, nx], [B, nu, nu], [B, nx, nx], each nullable
 };
 
 // elements of one workspace slot: the captured linearisation scalars and the gains of N stages

@@ -1,5 +1,5 @@
-// mpcb_vjp.hip — vector-Jacobian product of the SQP_RTI step in iterate mode (mpcb_solve_vjp,
-// include/mpcb.h) for the 12/4 model (gfx950 / MI355X).
+// mpcb_vjp.hip — vector-Jacobian product of the SQP_RTI step in iterate mode (mpcb_solve_vjp and
+// mpcb_solve_vjp_w, include/mpcb.h) for the 12/4 model (gfx950 / MI355X).
 //
 // With the linearisation point (xbar, ubar) and the active set held fixed, (X, U) of
 // mpcb_solve_iterate is an affine function of (x0, xref, uref).  The transpose of that map applied
@@ -37,7 +37,14 @@ namespace {
 
 constexpr int VJP_KR = 4;   // gain values per lane and stage: lane j < NX column j of K, lane NX+m kff[m]
 
-template <class T, int BOX>
+// WG: also the weight gradients (mpcb_solve_vjp_w).  At a fixed linearisation point and active set
+//   gQ = -s sym(sum_{k<N} dx_k rx_k^T),  gR = -s sym(sum_{k<N} du_k ru_k^T),  gQN = -sym(dx_N rx_N^T),
+// rx_k = X_k - xref_k, ru_k = U_k - uref_k the residuals of the solve's output, sym(M) = (M + M^T)/2.
+// Pass 3 holds (dx_k, du_k) in every lane: lane j < NX accumulates row j of the Q sum, lane NX + m
+// row m of the R sum, per instance (the caller sums over the batch; no atomics).  X, U and the
+// references are read in pass 1 by the lane that owns the stage, for the check sum, and again in
+// pass 3.  The rows meet in LDS, where entry (r, c), c <= r, is formed once and stored to both places.
+template <class T, int BOX, int WG>
 __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
   __shared__ GroupLds<T> lds_all[GROUPS];
   const int lane = threadIdx.x;
@@ -67,6 +74,11 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
     const T* ubp = a.ubar + b * (int64_t)N * NU;
     const T* gXp = a.gX ? a.gX + b * (int64_t)(N + 1) * NX : nullptr;
     const T* gUp = a.gU ? a.gU + b * (int64_t)N * NU : nullptr;
+    // (WG) the solve's output and its references
+    const T* Xp = WG ? a.X + b * (int64_t)(N + 1) * NX : nullptr;
+    const T* Up = WG ? a.U + b * (int64_t)N * NU : nullptr;
+    const T* xrp = WG ? a.xref + b * a.xref_sb : nullptr;
+    const T* urp = WG ? a.uref + b * a.uref_sb : nullptr;
 
     // ------------------------------------------------------------------ pass 1: nominal
     // (xbar_N is not read: no gap is formed and the terminal stage has no dynamics)
@@ -92,6 +104,23 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
           chk += u * T(0);
           fix[m] |= (uint64_t)((u <= W.lbu[m] || u >= W.ubu[m]) ? 1 : 0) << k;
         }
+      }
+      if constexpr (WG) {
+        // what pass 3 reads again for the residuals joins the check sum here (U: above with the box)
+#pragma unroll
+        for (int i = 0; i < NX; ++i) chk += Xp[(int64_t)k * NX + i] * T(0) + xrp[(int64_t)k * NX + i] * T(0);
+#pragma unroll
+        for (int m = 0; m < NU; ++m) chk += urp[(int64_t)k * NU + m] * T(0);
+        if constexpr (!BOX) {
+#pragma unroll
+          for (int m = 0; m < NU; ++m) chk += Up[(int64_t)k * NU + m] * T(0);
+        }
+      }
+    }
+    if constexpr (WG) {
+      if (j == 15) {   // the terminal stage, on the lane with the fewest stages
+#pragma unroll
+        for (int i = 0; i < NX; ++i) chk += Xp[(int64_t)N * NX + i] * T(0) + xrp[(int64_t)N * NX + i] * T(0);
       }
     }
     if constexpr (BOX) {
@@ -256,10 +285,27 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
       a.status[b] = bad ? MPCB_STATUS_NAN : (qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL);
 
     // ------------------------------------------------------------------ pass 3: forward
-    if (a.gxref || a.guref) {
+    // (the two pointers are read here in both variants: read inside the stage loop they would stand
+    // among its loads in the weight variant only, see the note on operand order below)
+    T* const gxrefp = a.gxref;
+    T* const gurefp = a.guref;
+    if (WG || gxrefp || gurefp) {
       T dxk[NX];
 #pragma unroll
       for (int i = 0; i < NX; ++i) dxk[i] = T(0);
+      // (WG) the lane's row of the running outer-product sums lives in LDS, which pass 2 is done
+      // with: row j of the Q sum in L.P (state lanes), row m of the R sum in L.hv (input lanes);
+      // the residual it multiplies is read through the lane's own pair of pointers
+      const T* const zp = j < NX ? Xp : Up;
+      const T* const rp = j < NX ? xrp : urp;
+      const int zw = j < NX ? NX : NU;
+      T* const wrow = j < NX ? &L.P[j * NX] : &L.hv[ju * NU];
+      if constexpr (WG) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+          if (i < NU || j < NX) wrow[i] = T(0);
+        }
+      }
       for (int k = 0; k < N; ++k) {
         T duk[NU];
 #pragma unroll
@@ -282,22 +328,80 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
         const T v = bad ? qnan : s * acc;
         if (valid) {
           if (j < NX) {
-            if (a.gxref) a.gxref[(b * (N + 1) + k) * NX + j] = v;
+            if (gxrefp) gxrefp[(b * (N + 1) + k) * NX + j] = v;
           } else {
-            if (a.guref) a.guref[(b * N + k) * NU + ju] = v;
+            if (gurefp) gurefp[(b * N + k) * NU + ju] = v;
           }
         }
         const T* cc = CC + ((int64_t)k * GROUPS + q) * LIN_STAGE;
         T dphi[NX];
         rk4_tan<T>(cc, dxk, duk, a.h, a.M, dphi);
+        if constexpr (WG) {
+          // row j of dx_k rx_k^T (state lanes) / row m of du_k ru_k^T (input lanes: NU entries).
+          // gxref and guref must keep the bits of the plain kernel, and the compiler decides which
+          // product of a sum of two it fuses from the order of the operands, which its
+          // reassociation pass takes from where the loads they descend from stand in the block.
+          // So this comes behind everything the plain kernel does in a stage, keeps its sums in
+          // LDS and not in registers, and reads du_k[ju] through an unrolled loop like the plain
+          // kernel's own loops over duk: with sel<NU>(duk, ju) the array left memory earlier in
+          // the pipeline in one instantiation, its loads left the block, and dx_{k+1} differed
+          // in the last bit.  (Check: the optimised IR of the stage loop, operand for operand.)
+          T zu = duk[0];
+#pragma unroll
+          for (int m = 1; m < NU; ++m) zu = (m == ju) ? duk[m] : zu;
+          const T zj = j < NX ? sel<NX>(dxk, jx) : zu;
+          const int64_t o = (int64_t)k * zw;
+#pragma unroll
+          for (int i = 0; i < NX; ++i) {
+            if (i < NU || j < NX) wrow[i] += zj * (zp[o + i] - rp[o + i]);
+          }
+        }
 #pragma unroll
         for (int i = 0; i < NX; ++i) dxk[i] = dphi[i];
       }
-      if (valid && a.gxref && j < NX) {
+      if (valid && gxrefp && j < NX) {
         T acc = T(0);
 #pragma unroll
         for (int i = 0; i < NX; ++i) acc += W.QN[jx * NX + i] * dxk[i];
-        a.gxref[(b * (N + 1) + N) * NX + j] = bad ? qnan : acc;
+        gxrefp[(b * (N + 1) + N) * NX + j] = bad ? qnan : acc;
+      }
+      if constexpr (WG) {
+        // the rows are in LDS; the terminal product joins them in L.X (stride NX)
+        if (j < NX) {
+          const T zj = sel<NX>(dxk, jx);
+#pragma unroll
+          for (int i = 0; i < NX; ++i)
+            L.X[j * NX + i] = zj * (Xp[(int64_t)N * NX + i] - xrp[(int64_t)N * NX + i]);
+        }
+        __syncthreads();
+        // symmetric by construction: entry (r, c), c <= r, is formed once by lane r and stored twice
+        const T hs = T(-0.5) * s;
+        if (j < NX) {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) {
+            if (i <= j && valid) {
+              const T vq = bad ? qnan : hs * (L.P[j * NX + i] + L.P[i * NX + j]);
+              const T vn = bad ? qnan : T(-0.5) * (L.X[j * NX + i] + L.X[i * NX + j]);
+              if (a.gQ) {
+                a.gQ[b * (NX * NX) + j * NX + i] = vq;
+                a.gQ[b * (NX * NX) + i * NX + j] = vq;
+              }
+              if (a.gQN) {
+                a.gQN[b * (NX * NX) + j * NX + i] = vn;
+                a.gQN[b * (NX * NX) + i * NX + j] = vn;
+              }
+            }
+          }
+        } else {
+#pragma unroll
+          for (int n = 0; n < NU; ++n) {
+            if (n <= ju && valid && a.gR) {
+              const T vr = bad ? qnan : hs * (L.hv[ju * NU + n] + L.hv[n * NU + ju]);
+              a.gR[b * (NU * NU) + ju * NU + n] = vr;
+              a.gR[b * (NU * NU) + n * NU + ju] = vr;
+            }
+          }
+        }
       }
     }
     __syncthreads();   // the next wave of the stride rewrites the slot
@@ -309,10 +413,15 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
 int64_t vjp_slot_elems(int N) { return (int64_t)N * (GROUPS * LIN_STAGE + 64 * VJP_KR); }
 
 template <class T> hipError_t launch_vjp(const VjpArgs<T>& a, int grid, hipStream_t st) {
-  if (a.box)
-    hipLaunchKernelGGL((vjp_kernel<T, 1>), dim3(grid), dim3(64), 0, st, a);
+  const bool wg = a.gQ || a.gR || a.gQN;   // no weight gradient asked for: the plain kernels
+  if (a.box && wg)
+    hipLaunchKernelGGL((vjp_kernel<T, 1, 1>), dim3(grid), dim3(64), 0, st, a);
+  else if (wg)
+    hipLaunchKernelGGL((vjp_kernel<T, 0, 1>), dim3(grid), dim3(64), 0, st, a);
+  else if (a.box)
+    hipLaunchKernelGGL((vjp_kernel<T, 1, 0>), dim3(grid), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((vjp_kernel<T, 0>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((vjp_kernel<T, 0, 0>), dim3(grid), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

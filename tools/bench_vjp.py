@@ -14,7 +14,10 @@ set; the cotangents are standard normal.  HIP events around ``--inner`` back-to-
 of ``--runs`` after ``--warmup`` calls of every variant, the variants alternating so drift hits
 them alike.  Prints one JSON line per shape.
 
-    python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4]
+``--weights`` adds mpcb_solve_vjp_w with all six outputs (X and U: the timed solve's) and its ratio
+to the plain product on the same build.
+
+    python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4] [--weights]
 """
 import argparse
 import json
@@ -49,7 +52,7 @@ def _handle(N, dtype, box, B, env):
                 os.environ[k] = v
 
 
-def bench(name, runs, warmup, inner):
+def bench(name, runs, warmup, inner, weights=False):
     import torch
 
     from mpc_blaster_amd import _lib
@@ -86,6 +89,12 @@ def bench(name, runs, warmup, inner):
         'vjp': lambda: _lib.check(m.lib.mpcb_solve_vjp(m._h, B, P(xbar), P(ubar), P(U) if box else null, null, 0,
                                                        P(gX), P(gU), P(gx0), P(gxr), P(gur), P(st_v), st)),
     }
+    if weights:   # all six gradients in one launch; X and U are the timed solve's outputs
+        gQ, gR = torch.empty((B, 12, 12), dtype=dt, device=dev), torch.empty((B, 4, 4), dtype=dt, device=dev)
+        gQN, st_w = torch.empty_like(gQ), torch.empty_like(st_v)
+        variants['vjp_w'] = lambda: _lib.check(m.lib.mpcb_solve_vjp_w(
+            m._h, B, P(xbar), P(ubar), P(X), P(U), P(xr), xr_sb, P(ur), 0, null, 0, P(gX), P(gU), P(gx0), P(gxr),
+            P(gur), P(gQ), P(gR), P(gQN), P(st_w), st))
     for _ in range(warmup):
         for f in variants.values():
             f()
@@ -108,6 +117,8 @@ def bench(name, runs, warmup, inner):
                vjp_over_single=round(med['vjp'] / med['solve_iterate_single'], 3),
                solve_status_ok=int((st_s == 0).sum()), vjp_status_ok=int((st_v == 0).sum()),
                clamped_fraction=(float(((U <= 0.0) | (U >= 65.0)).double().mean()) if box else 0.0))
+    if weights:
+        out.update(vjp_w_over_vjp=round(med['vjp_w'] / med['vjp'], 3), vjp_w_status_ok=int((st_w == 0).sum()))
     print(json.dumps(out), flush=True)
     return out
 
@@ -118,9 +129,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--inner', type=int, default=5, help='launches per event pair')
     ap.add_argument('--shapes', default='c2,c3,c4')
+    ap.add_argument('--weights', action='store_true',
+                    help='also time mpcb_solve_vjp_w (the weight gradients gQ, gR, gQN in the same launch)')
     a = ap.parse_args()
     for name in a.shapes.split(','):
-        bench(name, a.runs, a.warmup, a.inner)
+        bench(name, a.runs, a.warmup, a.inner, a.weights)
 
 
 if __name__ == '__main__':
