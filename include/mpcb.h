@@ -274,6 +274,50 @@ int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B,
                      int32_t* status, void* hip_stream);
 
 /*
+ * The product and the weight gradients of mpcb_solve_vjp / mpcb_solve_vjp_w for the full 17/6 model
+ * (nx = 17, nu = 6; both dtypes).  The adjoint problem (linear terms (-gX, -gU), no gaps, dx_0 = 0),
+ * the outputs gx0, gxref_k = s Q dx_k, gxref_N = QN dx_N, guref_k = s R du_k, the weight formulas
+ * and their symmetry convention, per-instance results without atomics (bitwise symmetric gQ, gR,
+ * gQN), the NaN rule, MPCB_STATUS_QP_FAIL for a masked input Hessian that is not positive definite
+ * and the first-call allocation of the call's own workspace are those of the two 12/4 entry points
+ * above, word for word.  What differs:
+ *   fixed [B,N,6] uint8   the active set, given by the caller: nonzero = component (k, m) is clamped;
+ *                         NULL = nothing is clamped.  The 17/6 boxes are solved by an interior
+ *                         point, so U lies near its bounds and not on them, and no rule on U's bits
+ *                         recovers the set: the caller derives it (a tolerance on U - lbu and
+ *                         ubu - U; BatchedMPC.solve_iterate_vjp does that).  The product is exact
+ *                         for the mask it is given, on any accepted handle whatever its box_u.  A
+ *                         clamped component has du = 0 and a zero row of K (the stage's input
+ *                         system with its row and column zeroed, the diagonal set to 1, and its
+ *                         rows of H_ux and h_u zeroed); its guref entry is row m of s R du, which
+ *                         is 0 for a diagonal R.  A stage with all six components clamped is valid.
+ *   X, U, xref, uref      read only when a weight output is requested (then required, and part of
+ *                         the NaN rule); U plays no part in the active set
+ *   parameters            the handle's mpcb_set_params array with its strides, or the defaults:
+ *                         what mpcb_solve_iterate reads.  B beyond the array's instance rows is
+ *                         MPCB_E_INVALID unless it is broadcast.  A non-finite parameter joins the
+ *                         NaN rule.  They are constants of the product: no gradient is offered.
+ *   any of the six outputs may be NULL, not all; gx0, gxref and guref have the same bits with and
+ *   without weight outputs
+ * MPCB_E_UNSUPPORTED on a 12/4 handle, and on a handle with box_x: an active state row is a state
+ * equality of the adjoint problem, which this call does not solve.  A caller who has checked that
+ * no state row is active can use a handle with the same definition and no box_x.  MPCB_E_INVALID:
+ * no cotangent, no output, B > max_batch, a weight output without X, U, xref or uref, a negative
+ * stride.  Large batches run in the chunks of the handle's solves; the workspace holds one chunk,
+ * is allocated by the first call (MPCB_E_NOMEM) and is not counted by mpcb_workspace_bytes.
+ */
+int mpcb_solve_vjp17(mpcb_handle* h, int64_t B,
+                     const void* xbar, const void* ubar,
+                     const uint8_t* fixed,
+                     const void* X, const void* U,
+                     const void* xref, int64_t xref_sb,
+                     const void* uref, int64_t uref_sb,
+                     const void* gX, const void* gU,
+                     void* gx0, void* gxref, void* guref,
+                     void* gQ, void* gR, void* gQN,
+                     int32_t* status, void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */

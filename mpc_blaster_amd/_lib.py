@@ -23,6 +23,9 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
            'mpcb_last_timing', 'mpcb_set_params', 'mpcb_set_t_blast', 'mpcb_qp_stats', 'mpcb_poc_jacobians',
            'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp',
            'mpcb_solve_vjp_w', 'mpcb_set_weights')
+# ... and the entry points named after the 17/6 model's dimensions (the list above is held to the
+# header's names by a letters-only pattern; tests/test_gpu_vjp17.py checks these)
+EXPORTS_17 = ('mpcb_solve_vjp17',)
 # the timing / launch-log slots of the split path (mpcb_last_timing, mpcb_plan_kernels) and of the
 # 17/6 model
 PHASES_12 = ('nominal', 'riccati', 'forward', 'linearise')
@@ -107,6 +110,13 @@ def load(path: str | None = None):
         # (mpcb_set_params gained two arguments in v4), so refuse it before any call
         raise LibraryMissing(f'{p} has C ABI version {got}, this binding expects {ABI_VERSION}: '
                              'rebuild it (__graft_entry__.build())')
+    # (typed after the version check: the entry point joined ABI version 5 without a new number, so
+    # a library of that version from before it is told apart by the missing symbol)
+    if not hasattr(lib, 'mpcb_solve_vjp17'):
+        raise LibraryMissing(f'{p} has no mpcb_solve_vjp17: rebuild it (__graft_entry__.build())')
+    lib.mpcb_solve_vjp17.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp]
+    lib.mpcb_solve_vjp17.restype = i32
     if path is None:
         _lib = lib
     return lib

@@ -201,8 +201,8 @@ class BatchedMPC:
         return out
 
     def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None, X=None, x_ref=None,
-                          u_ref=None, weights=False):
-        """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 12/4 model): with J the
+                          u_ref=None, weights=False, fixed=None, active_tol=None):
+        """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 17/6: below): with J the
         Jacobian of (X, U) with respect to (x0, x_ref, u_ref) at fixed xbar, ubar, wind, weights
         and active set, returns J^T (gX, gU) as a dict of device tensors ``gx0`` [B,12],
         ``gxref`` [B,N+1,12], ``guref`` [B,N,4] and ``status`` [B] (int32).  ``gX`` [B,N+1,12] and
@@ -215,7 +215,23 @@ class BatchedMPC:
         the cost weights, per instance: ``gQ`` [B,12,12], ``gR`` [B,4,4], ``gQN`` [B,12,12],
         symmetric; for a symmetric perturbation dQ the loss changes by <gQ.sum(0), dQ>.  It needs
         the solve's output ``X`` [B,N+1,12] and ``U`` and its references ``x_ref`` [B|1,N+1,12],
-        ``u_ref`` [B|1,N,4] (include/mpcb.h has the formula)."""
+        ``u_ref`` [B|1,N,4] (include/mpcb.h has the formula).
+
+        On a 17/6 handle (mpcb_solve_vjp17; shapes with 17 and 6) the active set is an argument,
+        because the interior point leaves U near its bounds and not on them: ``fixed`` is a
+        bool / uint8 tensor [B,N,6], nonzero = clamped.  Without it, and with ``U`` on an input-box
+        handle, the mask is ``(U <= lbu + active_tol) | (U >= ubu - active_tol)``; ``active_tol``
+        defaults to 1e-6 on an f64 handle (the tolerance the oracle's KKT certificate calls a
+        component active at) and has no default on an f32 handle, whose interior point stops near
+        mu = 1e-6: omitting it there raises ``ValueError``.  Without ``fixed`` and ``U`` nothing is
+        clamped.  The mask used is returned as ``fixed``.  A handle with the state box is refused;
+        ``wind`` raises as in ``solve_iterate``."""
+        if self.nx == 17:
+            return self._solve_iterate_vjp17(xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed,
+                                             active_tol)
+        if fixed is not None or active_tol is not None:
+            raise ValueError('fixed / active_tol belong to the 17/6 model: the 12/4 product reads its active '
+                             'set from U')
         torch = _torch()
         N = self.cfg.N
         xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar')
@@ -255,13 +271,83 @@ class BatchedMPC:
             self._ptr(out['guref']), self._ptr(out['status']), self._stream()))
         return out
 
-    def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None):
+    def active_mask17(self, U, active_tol=None):
+        """The 17/6 active set of ``U`` [B,N,6] by tolerance: a uint8 tensor, 1 where
+        ``U <= lbu + active_tol`` or ``U >= ubu - active_tol`` (``solve_iterate_vjp`` has the
+        default and why an f32 handle has none); None on a handle without the input box."""
+        if not self.cfg.boxed:
+            return None
+        if active_tol is None:
+            if self.cfg.dtype != 'f64':
+                raise ValueError('active_tol is required on an f32 17/6 handle: its interior point stops near '
+                                 'mu = 1e-6, so no fixed number separates active from inactive components')
+            active_tol = 1e-6
+        torch = _torch()
+        lb = torch.as_tensor(np.broadcast_to(np.asarray(self.cfg.lbu, dtype=np.float64), (self.nu,)).copy(),
+                             dtype=self.dtype, device=self._tdev)
+        ub = torch.as_tensor(np.broadcast_to(np.asarray(self.cfg.ubu, dtype=np.float64), (self.nu,)).copy(),
+                             dtype=self.dtype, device=self._tdev)
+        return ((U <= lb + active_tol) | (U >= ub - active_tol)).to(torch.uint8).contiguous()
+
+    def _solve_iterate_vjp17(self, xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed, active_tol):
+        torch = _torch()
+        if wind is not None:
+            raise _lib.MpcbError('mpcb error -4: wind is a 12/4-model extension')
+        N = self.cfg.N
+        xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar')
+        B = xb.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        ub, _ = self._dev(ubar, (N, self.nu), 'ubar', B)
+        gXd = None if gX is None else self._dev(gX, (N + 1, self.nx), 'gX', B)[0]
+        gUd = None if gU is None else self._dev(gU, (N, self.nu), 'gU', B)[0]
+        Ud = None if U is None else self._dev(U, (N, self.nu), 'U', B)[0]
+        dev = self._tdev
+        if fixed is not None:
+            if isinstance(fixed, np.ndarray) and not fixed.flags.writeable:
+                fixed = fixed.copy()   # torch.as_tensor warns on read-only arrays
+            fx = torch.as_tensor(fixed, device=dev)
+            if tuple(fx.shape) != (B, N, self.nu):
+                raise ValueError(f'fixed: expected shape [{B}, {N}, {self.nu}], got {tuple(fx.shape)}')
+            fx = (fx != 0).to(torch.uint8).contiguous()
+        elif Ud is not None:
+            fx = self.active_mask17(Ud, active_tol)
+        else:
+            fx = None
+        out = dict(gx0=torch.empty((B, self.nx), dtype=self.dtype, device=dev),
+                   gxref=torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev),
+                   guref=torch.empty((B, N, self.nu), dtype=self.dtype, device=dev),
+                   status=torch.empty((B,), dtype=torch.int32, device=dev), fixed=fx)
+        Xd = xr = ur = None
+        xr_sb = ur_sb = 0
+        if weights:
+            if X is None or U is None or x_ref is None or u_ref is None:
+                raise ValueError('weights=True needs X, U, x_ref and u_ref of the solve')
+            Xd, _ = self._dev(X, (N + 1, self.nx), 'X', B)
+            xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
+            ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
+            out.update(gQ=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev),
+                       gR=torch.empty((B, self.nu, self.nu), dtype=self.dtype, device=dev),
+                       gQN=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev))
+        self._keep_vjp = (xb, ub, gXd, gUd, Ud, fx, Xd, xr, ur)
+        _lib.check(self.lib.mpcb_solve_vjp17(
+            self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(fx), self._ptr(Xd),
+            self._ptr(Ud if weights else None), self._ptr(xr), xr_sb, self._ptr(ur), ur_sb,
+            self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']), self._ptr(out['gxref']),
+            self._ptr(out['guref']), self._ptr(out.get('gQ')), self._ptr(out.get('gR')),
+            self._ptr(out.get('gQN')), self._ptr(out['status']), self._stream()))
+        return out
+
+    def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
+                           active_tol=None):
         """``solve_iterate`` as a differentiable torch operation: returns (u0, X, U) whose
         gradients flow to ``x0``, ``x_ref`` and ``u_ref`` and, when given, to the weight tensors
         ``Q``, ``R``, ``QN``, which the forward pass installs with ``set_weights`` (see
-        ``mpc_blaster_amd.autograd``)."""
+        ``mpc_blaster_amd.autograd``).  ``active_tol``: the 17/6 active-set tolerance of
+        ``solve_iterate_vjp``."""
         from .autograd import solve_iterate_diff
-        return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN)
+        return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN,
+                                  active_tol=active_tol)
 
     def set_weights(self, Q=None, R=None, QN=None):
         """New cost weights on this handle (mpcb_set_weights; acados ``cost_set(k, 'W', W)`` with

@@ -1,8 +1,9 @@
 """The SQP_RTI step as a differentiable torch operation.
 
-``solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None)
--> (u0, X, U)`` runs ``BatchedMPC.solve_iterate`` in the forward pass and one ``mpcb_solve_vjp``
-call (``mpcb_solve_vjp_w`` when a weight gradient is needed; include/mpcb.h) in the backward pass,
+``solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
+active_tol=None) -> (u0, X, U)`` runs ``BatchedMPC.solve_iterate`` in the forward pass and one
+``mpcb_solve_vjp`` call (``mpcb_solve_vjp17`` on the 17/6 model;
+``mpcb_solve_vjp_w`` when a weight gradient is needed; include/mpcb.h) in the backward pass,
 so a loss on ``u0``, ``X``, ``U`` can be differentiated with respect to ``x0``, ``x_ref``, ``u_ref``
 and the cost weights.
 
@@ -15,7 +16,14 @@ point has U strictly inside the box and gets the unconstrained gradient (include
 ``ubar`` and ``wind`` are constants (Gauss-Newton / RTI): their gradients are ``None``, as is that
 of the model.  An instance whose forward status is not 0 gets zero gradients.  A
 reference passed as one row (``[1, ...]`` or without a batch axis) receives the sum of the
-per-instance gradients.  12/4 model only; not differentiable twice.
+per-instance gradients.  Not differentiable twice.
+
+The 17/6 model (``mpcb_solve_vjp17``).  Its boxes are solved by an interior point, so U lies near
+its bounds and the active set is taken by tolerance: the forward pass derives the mask
+``(U <= lbu + active_tol) | (U >= ubu - active_tol)`` once (``BatchedMPC.active_mask17``: 1e-6 on an
+f64 handle, required on an f32 one) and the backward pass hands it to the kernel, which is exact
+for that mask.  A handle with the state box is refused (an active state row is not covered), and
+``wind`` raises as in ``solve_iterate``.  The weights work as on 12/4.
 
 The weights.  ``Q``, ``R``, ``QN`` are optional torch tensors: a vector (the diagonal) or a
 symmetric matrix.  The weights belong to the handle, so the forward pass installs the value of
@@ -45,8 +53,15 @@ def _function():
 
     class SolveIterate(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN):
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol):
             N = mpc.cfg.N
+            full = mpc.nx == 17
+            if full and mpc.cfg.lbx is not None:
+                raise ValueError('solve_iterate_diff does not cover the 17/6 state box: an active state row '
+                                 'is a state equality of the adjoint problem (use a handle without lbx/ubx '
+                                 'when no state row is active)')
+            if full and mpc.cfg.boxed and active_tol is None and mpc.cfg.dtype != 'f64':
+                raise ValueError('active_tol is required on an f32 17/6 input-box handle')
             x0d, _ = mpc._dev(x0.detach(), (mpc.nx,), 'x0')
             B = x0d.shape[0]
             xb, _ = mpc._dev(xbar.detach() if torch.is_tensor(xbar) else xbar, (N + 1, mpc.nx), 'xbar', B)
@@ -62,6 +77,9 @@ def _function():
             u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd)   # fresh outputs
             X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
             ctx.mpc = mpc
+            ctx.full = full
+            # (17/6) the active set by tolerance, derived once from the forward solve's U
+            ctx.fixed = mpc.active_mask17(U, active_tol) if full else None
             ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
             ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
             ctx.has_wind = wd is not None
@@ -80,6 +98,7 @@ def _function():
             xb, ub, U, status = ctx.saved_tensors[:4]
             wd = ctx.saved_tensors[4] if ctx.has_wind else None
             need = ctx.needs_input_grad
+            kw = dict(fixed=ctx.fixed) if ctx.full else dict(wind=wd)
             want_w = ctx.has_weights and any(need[7:10])
             gU = g_U.to(mpc.dtype).clone()
             gU[:, 0] += g_u0.to(mpc.dtype)
@@ -89,10 +108,10 @@ def _function():
                                        '(set_weights or another forward with weight tensors): the '
                                        'weight gradient needs the weights the forward solved with')
                 X, xr, ur = ctx.saved_tensors[-3:]
-                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd, X=X, x_ref=xr, u_ref=ur,
-                                            weights=True)
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, X=X, x_ref=xr, u_ref=ur, weights=True,
+                                            **kw)
             else:
-                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd)
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=None if ctx.full else U, **kw)
             ok = status == 0
             grads = []
             for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
@@ -109,18 +128,20 @@ def _function():
                     g = torch.where(ok.reshape(-1, 1, 1), out[key], torch.zeros_like(out[key])).sum(dim=0)
                     wgrads[i] = (torch.diagonal(g) if len(shape) == 1 else g).reshape(shape).to(dt)
             return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
-                    grads[2] if need[5] else None, None, *wgrads)
+                    grads[2] if need[5] else None, None, *wgrads, None)
 
     _FN = SolveIterate
     return _FN
 
 
-def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None):
-    """(u0 [B,4], X [B,N+1,12], U [B,N,4]) of ``mpc.solve_iterate``, differentiable with respect to
-    the torch tensors ``x0``, ``x_ref`` and ``u_ref`` and, when given, the weight tensors ``Q``, ``R``,
+def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
+                       active_tol=None):
+    """(u0 [B,4], X [B,N+1,12], U [B,N,4]; 17 and 6 on the full model) of ``mpc.solve_iterate``,
+    differentiable with respect to the torch tensors ``x0``, ``x_ref`` and ``u_ref`` and, when given, the weight tensors ``Q``, ``R``,
     ``QN`` (vectors or symmetric matrices; installed on the handle by the forward pass, a host
-    synchronisation: module docstring).  The per-instance status is ``mpc.get_status()``."""
+    synchronisation: module docstring).  ``active_tol``: the 17/6 active-set tolerance (module
+    docstring).  The per-instance status is ``mpc.get_status()``."""
     import torch
     x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
                         for t in (x0, x_ref, u_ref))
-    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN)
+    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol)

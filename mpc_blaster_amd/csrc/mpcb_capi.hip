@@ -102,6 +102,8 @@ struct mpcb_handle {
   void* vjp_scratch = nullptr;   // mpcb_solve_vjp's slot workspace: allocated by its first call, not
                                  // counted in scratch_bytes
   int vjp_grid = 0;              // ... and its resident slots
+  void* vjp17_scratch = nullptr; // mpcb_solve_vjp17's chunk workspace: allocated by its first call, not
+                                 // counted in scratch_bytes
 };
 
 // A 17/6 call over B instances may only read parameter rows that exist (mpcb_set_params count).
@@ -501,6 +503,7 @@ extern "C" int mpcb_destroy(mpcb_handle* h) {
   if (h->qp_stats) (void)hipFree(h->qp_stats);
   if (h->u_scratch) (void)hipFree(h->u_scratch);
   if (h->vjp_scratch) (void)hipFree(h->vjp_scratch);
+  if (h->vjp17_scratch) (void)hipFree(h->vjp17_scratch);
   delete h;
   return MPCB_OK;
 }
@@ -996,6 +999,74 @@ extern "C" int mpcb_solve_vjp(mpcb_handle* h, int64_t B, const void* xbar, const
                               void* gxref, void* guref, int32_t* status, void* stream) {
   return mpcb_solve_vjp_w(h, B, xbar, ubar, nullptr, U, nullptr, 0, nullptr, 0, wind, wind_sb, gX, gU, gx0,
                           gxref, guref, nullptr, nullptr, nullptr, status, stream);
+}
+
+template <class T>
+static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const uint8_t* fixed,
+                      const void* X, const void* U, const void* xref, int64_t xref_sb, const void* uref,
+                      int64_t uref_sb, const void* gX, const void* gU, void* gx0, void* gxref, void* guref,
+                      void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
+  const int N = h->cfg.N;
+  if (!h->vjp17_scratch) {   // one chunk of the handle's 17/6 solves, in whole wavefronts
+    const size_t bytes = (size_t)vjp17_elems(N) * sizeof(T) * (size_t)((h->chunk + 3) / 4 * 4);
+    const hipError_t e = hipMalloc(&h->vjp17_scratch, bytes);
+    if (e != hipSuccess) {
+      h->vjp17_scratch = nullptr;
+      return fail(MPCB_E_NOMEM, "vjp17 workspace %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+  }
+  Vjp17Args<T> a;
+  a.N = N;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
+  a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
+  a.fixed = fixed;
+  a.X = (const T*)X; a.U = (const T*)U;
+  a.xref = (const T*)xref; a.xref_sb = xref_sb;
+  a.uref = (const T*)uref; a.uref_sb = uref_sb;
+  a.gX = (const T*)gX; a.gU = (const T*)gU;
+  a.gx0 = (T*)gx0; a.gxref = (T*)gxref; a.guref = (T*)guref;
+  a.gQ = (T*)gQ; a.gR = (T*)gR; a.gQN = (T*)gQN;
+  a.status = status;
+  a.ws = (T*)h->vjp17_scratch;
+  for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
+    a.b0 = b0;
+    a.nb = (B - b0 < h->chunk) ? B - b0 : h->chunk;
+    const hipError_t e = launch_vjp17<T>(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MPCB_E_HIP, "vjp17 launch: %s", hipGetErrorString(e));
+  }
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar,
+                                const uint8_t* fixed, const void* X, const void* U, const void* xref,
+                                int64_t xref_sb, const void* uref, int64_t uref_sb, const void* gX,
+                                const void* gU, void* gx0, void* gxref, void* guref, void* gQ, void* gR,
+                                void* gQN, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_vjp17 covers the 17/6 model (12/4: mpcb_solve_vjp)");
+  if (h->cfg.box_x)
+    return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product does not cover the state box (active state rows)");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  const bool wg = gQ || gR || gQN;
+  if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
+  if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (wg && (!X || !U || !xref || !uref))
+    return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
+  if (wg && (xref_sb < 0 || uref_sb < 0)) return fail(MPCB_E_INVALID, "negative reference stride");
+  if (int rc = check_params(h, B)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->cfg.dtype == MPCB_F64)
+    return vjp17_impl<double>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref,
+                              guref, gQ, gR, gQN, status, stream);
+  return vjp17_impl<float>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref,
+                           guref, gQ, gR, gQN, status, stream);
 }
 
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,

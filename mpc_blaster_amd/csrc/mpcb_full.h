@@ -428,6 +428,48 @@ constexpr int IPM17_SBOX_SHORT_RUN = 7;
 // against the fp64 oracle in tests/test_gpu_full17.py
 constexpr double IPM17_TOL_F32 = 1e-6, IPM17_BREAK_F32 = 1e-3, IPM17_RES_F32 = 1e-5;
 
+// ---- mpcb_solve_vjp17 (mpcb_r17.hip): the vector-Jacobian product of the 17/6 RTI step ---------
+template <class T>
+struct Vjp17Args {
+  int64_t b0, nb;    // first global instance of the chunk, instances in the chunk
+  int N;
+  T h, s;
+  Model<T> M;
+  const Weights17<T>* W;
+  const T* p; int64_t p_sb, p_kb;   // parameters as FullArgs; nullptr -> W->p
+  const T* xbar; const T* ubar;     // the linearisation point
+  const uint8_t* fixed;             // [B][N][6] nonzero = clamped (nullable: nothing clamped)
+  const T* X; const T* U;           // weight gradients only: the solve's output ...
+  const T* xref; int64_t xref_sb;   // ... and its references
+  const T* uref; int64_t uref_sb;
+  const T* gX; const T* gU;         // cotangents (one may be null)
+  T* gx0; T* gxref; T* guref;
+  T* gQ; T* gR; T* gQN;
+  int32_t* status;
+  T* ws;             // the call's own chunk workspace: per instance vjp17_elems(N) elements
+};
+
+// Per-instance workspace carve of the product (Vjp17Args::ws): the linearisation in Ws17::AB's
+// column layout, the gains in Ws17::KR's, the adjoint trajectory (dx, du) for the weight sums, a
+// sink of the same shape as (gxref, guref) for the stores of outputs nobody asked for, and one
+// check value per stage from the linearisation kernel (0, or NaN for a non-finite input).
+__host__ __device__ constexpr int64_t vjp17_elems(int N) {
+  return (int64_t)N * (NZ17 * NX17 + NU17 * NX17 + NU17) + 2 * ((int64_t)(N + 1) * NX17 + (int64_t)N * NU17) + N;
+}
+template <class T>
+struct WsV17 {
+  T *AB, *KR, *DX, *DU, *SK, *CK;
+  __device__ __forceinline__ WsV17(T* ws, int N) {
+    AB = ws;                                     // [N][23][17]
+    KR = AB + (int64_t)N * NZ17 * NX17;          // [N][6*17 + 6]
+    DX = KR + (int64_t)N * Ws17<T>::KR_N;        // [N+1][17]
+    DU = DX + (int64_t)(N + 1) * NX17;           // [N][6]
+    SK = DU + (int64_t)N * NU17;                 // [N+1][17] | [N][6]
+    CK = SK + (int64_t)(N + 1) * NX17 + (int64_t)N * NU17;   // [N]
+  }
+};
+template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st);
+
 // ev (nullable): 4 events recorded before nominal17, after it, after lin17ws and after riccati17.
 template <class T> hipError_t launch_full17(const FullArgs<T>& a, hipStream_t st, hipEvent_t* ev = nullptr);
 template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_t st);

@@ -1357,6 +1357,423 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
   if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : st;
 }
 
+// ---- mpcb_solve_vjp17: the vector-Jacobian product of the 17/6 RTI step ------------------------
+// At a fixed linearisation point and active set (X, U) of mpcb_solve_iterate is affine in
+// (x0, xref, uref); its transpose applied to (gX, gU) is one more LQ solve over the same [A_k|B_k]
+// with linear terms (-gX, -gU), no gaps, dx_0 = 0 and the clamped input components masked out
+// (include/mpcb.h, mpcb_vjp.hip for the 12/4 model).  Three launches per chunk:
+//   vjp17_lin_kernel   [A_k|B_k] at the caller's (xbar, ubar) into the call's own workspace
+//                      (lin17_packed: the solver's arithmetic), one check value per stage;
+//   vjp17_kernel       backward() without gaps, barrier terms or cost residuals, the 6x6 system
+//                      masked by the stage's six mask bits, then gx0 = -p_0 and status; the forward
+//                      pass from dx_0 = 0 writes gxref_k = s Q dx_k, guref_k = s R du_k, QN dx_N and
+//                      keeps (dx, du) for
+//   vjp17_w_kernel     the three symmetrised outer-product sums, only with a weight output.
+// One instantiation per precision serves every combination of outputs, so gx0, gxref and guref
+// cannot depend on whether the weight sums are asked for.
+
+template <class T>
+__global__ void __launch_bounds__(64) vjp17_lin_kernel(Vjp17Args<T> a) {
+  const int lane = threadIdx.x;
+  const int t = lane % LQ17;
+  const int N = a.N;
+  const int64_t idx = (int64_t)blockIdx.x * GQ17 + lane / LQ17;   // (instance, stage) pair
+  if (idx >= a.nb * N) return;
+  const int64_t c = idx / N;
+  const int k = (int)(idx % N);
+  const int64_t b = a.b0 + c;
+  const T* pb = a.p ? a.p + b * a.p_sb + k * a.p_kb : a.W->p;
+  WsV17<T> w(a.ws + c * vjp17_elems(N), N);
+  T* ABk = w.AB + (int64_t)k * NZ17 * NX17;
+  const T* xk = a.xbar + (b * (int64_t)(N + 1) + k) * NX17;
+  const T* uk = a.ubar + (b * (int64_t)N + k) * NU17;
+  if (t == 0) {   // the NaN rule: v * 0 of everything this stage loads
+    T chk = T(0);
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) chk += xk[i] * T(0);
+#pragma unroll
+    for (int m = 0; m < NU17; ++m) chk += uk[m] * T(0);
+#pragma unroll
+    for (int i = 0; i < NP17; ++i) chk += pb[i] * T(0);
+    w.CK[k] = chk;
+  }
+  lin17_packed<T>(t, pb, a.h, a.M, xk, uk,
+                  [&](int j, const T* v) {
+#pragma unroll
+                    for (int i = 0; i < NX17; ++i) ABk[j * NX17 + i] = v[i];
+                  },
+                  [&](const T*) {});   // (no gap is formed)
+}
+
+// Stage data of the adjoint Riccati pass, loaded one stage ahead as raw loads (Pre's rule)
+template <class T>
+struct PreV {
+  T ab[NX17];      // column z of [A_k | B_k]
+  T a8[5];         // the nonzeros of the implicit column 8
+  T gxs, gx8, gum; // gX_k[s], gX_k[8], gU_k[m]
+  uint8_t fx;      // the mask byte of input m (input lanes)
+};
+
+template <class T>
+__global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
+  __shared__ Lds<T> lds_all[GR];
+  __shared__ T sQ[NX17 * NX17];
+  __shared__ T sR[NU17 * NU17];
+  const int lane = threadIdx.x;
+  const int qi = lane / LN;
+  const int t = lane % LN;
+  const int64_t c = (int64_t)blockIdx.x * GR + qi;
+  const bool valid = c < a.nb;
+  // A ragged last wave's extra groups run on private padding slots of the workspace, which the
+  // linearisation never fills (riccati17q_kernel's note applies word for word): they read the last
+  // instance's arrays and write nothing but their own slot.
+  const int64_t b = a.b0 + (valid ? c : a.nb - 1);
+  const int N = a.N;
+  const Weights17<T>& W = *a.W;
+  const bool in = t >= 8 && t < 14;
+  const int s = sown(t);
+  const int z = zcol(t);
+  const int m = in ? t - 8 : 0;
+  for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
+  for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  __syncthreads();
+  const WsV17<T> w(a.ws + c * vjp17_elems(N), N);
+  Lds<T>& L = lds_all[qi];
+  constexpr int KR_N = Ws17<T>::KR_N;
+  const uint64_t m_in = lane_mask(in);
+  // a missing cotangent or mask: the loads go to the instance's own [A|B] block (readable, long
+  // enough) and the values are dropped, so the stage loop has no branch around a load
+  const bool hasX = a.gX != nullptr, hasU = a.gU != nullptr, hasF = a.fixed != nullptr;
+  const bool wg = a.gQ || a.gR || a.gQN;
+  const T* gXp = hasX ? a.gX + b * (int64_t)(N + 1) * NX17 : w.AB;
+  const T* gUp = hasU ? a.gU + b * (int64_t)N * NU17 : w.AB;
+  const uint8_t* fxp = hasF ? a.fixed + b * (int64_t)N * NU17 : reinterpret_cast<const uint8_t*>(w.AB);
+  const uint64_t m_x = lane_mask(hasX), m_u = lane_mask(hasU);
+
+  // ---- the NaN rule: the linearisation's stage values, and what the weight kernel reads later
+  T chk = T(0);
+  for (int k = t; k < N; k += LN) chk += w.CK[k];
+  if (wg) {
+    const T* Xp = a.X + b * (int64_t)(N + 1) * NX17;
+    const T* Up = a.U + b * (int64_t)N * NU17;
+    const T* xrp = a.xref + b * a.xref_sb;
+    const T* urp = a.uref + b * a.uref_sb;
+    for (int i = t; i < (N + 1) * NX17; i += LN) chk += Xp[i] * T(0) + xrp[i] * T(0);
+    for (int i = t; i < N * NU17; i += LN) chk += Up[i] * T(0) + urp[i] * T(0);
+  }
+
+  // ---- backward: P_N = QN, p_N = -gX_N
+  T Pc[NX17], P88, pj, p8;
+  {
+    const T gs = csel(m_x, gXp[(int64_t)N * NX17 + s], T(0));
+    const T g8 = csel(m_x, gXp[(int64_t)N * NX17 + OM], T(0));
+    chk += gs * T(0) + g8 * T(0);
+    pj = -gs;
+    p8 = -g8;
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) Pc[i] = W.QN[i * NX17 + s];
+    P88 = W.QN[OM * NX17 + OM];
+  }
+  auto prefetch = [&](int k, PreV<T>& p) {
+    const T* ABk = w.AB + (int64_t)k * NZ17 * NX17;
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) p.ab[i] = ABk[z * NX17 + i];
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) p.a8[r5] = ABk[OM * NX17 + c8row(r5)];
+    p.gxs = gXp[(int64_t)k * NX17 + s];
+    p.gx8 = gXp[(int64_t)k * NX17 + OM];
+    p.gum = gUp[(int64_t)k * NU17 + m];
+    p.fx = fxp[(int64_t)k * NU17 + m];
+  };
+  bool qp_ok = true;
+  PreV<T> nx;
+  prefetch(N - 1, nx);
+  for (int k = N - 1; k >= 0; --k) {
+    const PreV<T> cu = nx;
+    prefetch(k > 0 ? k - 1 : 0, nx);   // (unconditional: no branch join on the loads)
+    // the stage's six mask bits: the input lanes' bytes meet in a ballot, bit 16 qi + 8 + n
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(hasF && cu.fx != 0);
+    const unsigned fm = (unsigned)(bal >> (qi * LN + 8)) & 63u;
+    uint64_t mf[NU17];
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) mf[n] = lane_mask(((fm >> n) & 1u) != 0);
+    const T gxs = csel(m_x, cu.gxs, T(0)), gx8 = csel(m_x, cu.gx8, T(0)), gum = csel(m_u, cu.gum, T(0));
+    chk += gxs * T(0) + gx8 * T(0) + gum * T(0);
+    const T pt = pj, pt8 = p8;
+    // ---- Y = P [A|B]_z and h_AB = [A|B]_z^T p
+    T y[NX17], hab = T(0);
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) y[i] = T(0);
+    static_for<LN>([&](auto l) {
+      constexpr int tl = decltype(l)::value;
+      bc18<tl>(y, hab, Pc, pt, cu.ab[sown(tl)]);
+    });
+    diag16_sown(y, Pc[OM], cu.ab[OM]);
+    y[OM] += P88 * cu.ab[OM];
+    hab += pt8 * cu.ab[OM];
+    // ---- G_z = [A|B]^T Y_z
+    T g[LN];
+#pragma unroll
+    for (int i = 0; i < LN; ++i) g[i] = T(0);
+#pragma unroll
+    for (int l = 0; l < NX17; ++l) diag16(g, cu.ab[l], y[l]);
+    T g8 = T(0);
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) g8 += cu.a8[r5] * y[c8row(r5)];
+#pragma unroll
+    for (int ci = 0; ci < 6; ++ci) L.YC[ci][t] = y[ids(ci)];
+    wave_lds_sync();
+    // ---- input lanes: their column G[:, 17+m] + s R -> Huu, h_u = B^T p - gU, Hux[:, 8]
+    if (in) {
+#pragma unroll
+      for (int n = 0; n < NU17; ++n) L.HU[m][n] = g[8 + n] + sR[n * NU17 + m];
+      L.HU[m][6] = hab - gum;
+      L.HU[m][7] = g8;
+    }
+    wave_lds_sync();
+    // ---- this lane's state column Gs = G[:, s] (23 rows by z index) and gradient h_s
+    T Gs[NZ17];
+    {
+      const int ci = in ? m : 0;
+      T spc = T(0);
+#pragma unroll
+      for (int r5 = 0; r5 < 5; ++r5) spc += cu.a8[r5] * Pc[c8row(r5)];
+#pragma unroll
+      for (int tp = 0; tp < LN; ++tp) Gs[zcol(tp)] = csel(m_in, L.YC[ci][tp], g[tp]);
+#pragma unroll
+      for (int r6 = 0; r6 < 6; ++r6) Gs[ids(r6)] = csel(m_in, Pc[ids(r6)], y[ids(r6)]);
+      Gs[OM] = csel(m_in, spc, g8);
+    }
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) Gs[i] += sQ[i * NX17 + xpos(s)];
+    const T hs = (in ? pt : hab) - gxs;   // AB[:, c]^T p = p_c for an identity state
+    T spc_own = T(0);
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) spc_own += cu.a8[r5] * Pc[c8row(r5)];   // (P a)_s
+    T pa8 = P88 * cu.a8[0];                                                // (P a)_8
+    T G88, h8;
+    {
+      const T pc8 = Pc[OM];
+      pa8 += bcast<tstate(2)>(pc8) * cu.a8[1] + bcast<tstate(14)>(pc8) * cu.a8[2] +
+             bcast<tstate(15)>(pc8) * cu.a8[3] + bcast<tstate(16)>(pc8) * cu.a8[4];
+      G88 = cu.a8[0] * pa8 + cu.a8[1] * bcast<tstate(2)>(spc_own) + cu.a8[2] * bcast<tstate(14)>(spc_own) +
+            cu.a8[3] * bcast<tstate(15)>(spc_own) + cu.a8[4] * bcast<tstate(16)>(spc_own);
+      h8 = cu.a8[0] * pt8 + cu.a8[1] * bcast<tstate(2)>(pt) + cu.a8[2] * bcast<tstate(14)>(pt) +
+           cu.a8[3] * bcast<tstate(15)>(pt) + cu.a8[4] * bcast<tstate(16)>(pt) - gx8;
+      G88 += sQ[OM * NX17 + xpos(OM)];
+    }
+    // ---- Huu masked (oracle.ocp._masked_stage, delta = 0): row and column of a clamped input
+    // zeroed, diagonal 1, its rows of H_ux and h_u zeroed; Cholesky, k, K columns
+    T H[NU17 * NU17], hu[NU17], hx8[NU17];
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) H[i * NU17 + j] = csel(mf[i] | mf[j], T(i == j ? 1 : 0), L.HU[j][i]);
+      hu[i] = L.HU[i][6];
+      hx8[i] = L.HU[i][7];
+    }
+    T Lc[NU17 * NU17];
+    chol_n<T, NU17>(H, Lc);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) ok = ok && (Lc[i * NU17 + i] == Lc[i * NU17 + i]);
+    qp_ok = qp_ok && ok;
+    T kff[NU17], Ks[NU17], K8[NU17], nb[NU17];
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) nb[i] = csel(mf[i], T(0), -hu[i]);
+    chol_n_solve<T, NU17>(Lc, nb, kff);
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) nb[i] = csel(mf[i], T(0), -Gs[NX17 + i]);
+    chol_n_solve<T, NU17>(Lc, nb, Ks);
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) nb[i] = csel(mf[i], T(0), -hx8[i]);
+    chol_n_solve<T, NU17>(Lc, nb, K8);
+    {   // KR as backward() writes it: K row-major [6][17], then k[6]; unconditional stores
+      T* kr = w.KR + (int64_t)k * KR_N;
+#pragma unroll
+      for (int i = 0; i < NU17; ++i) {
+        kr[i * NX17 + s] = Ks[i];
+        kr[i * NX17 + OM] = K8[i];
+      }
+      kr[NU17 * NX17 + m] = sel<NU17>(kff, m);
+    }
+    // ---- P_new[:, s] = G_xx[:, s] + Hxu K[:, s] (the unmasked H_xu: K's clamped rows are 0)
+    T Pn[NX17];
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) Pn[i] = Gs[i];
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) {
+      diag16_sown(Pn, Gs[NX17 + n], Ks[n]);
+      Pn[OM] += hx8[n] * Ks[n];
+    }
+    T pn = hs, pn8 = h8, P88n = G88;
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) {
+      pn += Gs[NX17 + n] * kff[n];
+      pn8 += hx8[n] * kff[n];
+      P88n += hx8[n] * K8[n];
+    }
+    // symmetric by construction: entry (i, s) from the lane max(own, owner of i)
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) L.X[t][xpos(i)] = Pn[i];
+    wave_lds_sync();
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) {
+      if (i == OM) {
+        Pc[i] = Pn[i];
+      } else {
+        const T o = L.X[tstate(i)][xpos(s)];
+        Pc[i] = csel(lane_mask(tstate(i) > t), o, Pn[i]);
+      }
+    }
+    P88 = P88n;
+    pj = pn;
+    p8 = pn8;
+    wave_lds_sync();
+  }
+
+  // every input of the instance has been read: its check sum, the same in its 16 lanes
+  chk = sum16(chk);
+  const bool bad = chk != chk;
+  const T qnan = __builtin_nan("");
+  if (valid && a.gx0) {
+    a.gx0[b * NX17 + s] = bad ? qnan : -pj;
+    if (t == 0) a.gx0[b * NX17 + OM] = bad ? qnan : -p8;
+  }
+  if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : (qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL);
+  if (!a.gxref && !a.guref && !wg) return;
+  __syncthreads();   // K and k are read back across lanes
+
+  // ---- forward from dx_0 = 0 over the stored gains and the cached [A|B] (forward<>'s ring of
+  // stage rows, two deep), writing s Q dx_k, s R du_k and keeping (dx_k, du_k)
+  constexpr int FD = 2;
+  struct Row { T kr[LN], k8, kf, ab[LN], ab8o, c8s, c88; };
+  auto load = [&](int k, Row& o) {
+    const T* ABk = w.AB + (int64_t)k * NZ17 * NX17;
+    const T* Kk = w.KR + (int64_t)k * KR_N;
+#pragma unroll
+    for (int tp = 0; tp < LN; ++tp) o.kr[tp] = Kk[m * NX17 + sown(tp)];
+    o.k8 = Kk[m * NX17 + OM];
+    o.kf = Kk[NU17 * NX17 + m];
+#pragma unroll
+    for (int tp = 0; tp < LN; ++tp) o.ab[tp] = ABk[zcol(tp) * NX17 + s];
+    o.ab8o = ABk[z * NX17 + OM];
+    o.c8s = ABk[OM * NX17 + s];
+    o.c88 = ABk[OM * NX17 + OM];
+  };
+  const bool wx = valid && a.gxref, wu = valid && a.guref;
+  T* const oxs = wx ? a.gxref + b * (int64_t)(N + 1) * NX17 : w.SK;                       // [N+1][17]
+  T* const ous = wu ? a.guref + b * (int64_t)N * NU17 : w.SK + (int64_t)(N + 1) * NX17;   // [N][6]
+  T dxs = T(0), dx8 = T(0);
+  Row ring[FD];
+  static_for<FD>([&](auto sl) {
+    if (decltype(sl)::value < N) load(decltype(sl)::value, ring[decltype(sl)::value]);
+  });
+  auto stage = [&](int k, Row& cr) {
+    T du = cr.kf + cr.k8 * dx8;
+    chain16(du, dxs, cr.kr);
+    if (!in) du = T(0);
+    // row s of s Q, row 8 of s Q and row m of s R times (dx_k, du_k)
+    T wq[LN];
+#pragma unroll
+    for (int tp = 0; tp < LN; ++tp) wq[tp] = sQ[s * NX17 + xpos(sown(tp))];
+    T ox = sQ[s * NX17 + xpos(OM)] * dx8;
+    chain16(ox, dxs, wq);
+    const T ox8 = sum16(sQ[OM * NX17 + xpos(s)] * dxs, sQ[OM * NX17 + xpos(OM)] * dx8);
+    T ou = T(0);
+    static_for<NU17>([&](auto n) {
+      constexpr int n_ = decltype(n)::value;
+      ou += bcast<8 + n_>(du) * sR[m * NU17 + n_];
+    });
+    // stores without lane-divergent branches (forward<>'s note): each lane its own state, and the
+    // input lanes their input or (every other lane, the same value) the state-8 entry
+    w.DX[(int64_t)k * NX17 + s] = dxs;
+    T* d2 = in ? w.DU + (int64_t)k * NU17 + m : w.DX + (int64_t)k * NX17 + OM;
+    *d2 = in ? du : dx8;
+    oxs[(int64_t)k * NX17 + s] = bad ? qnan : ox;
+    T* o2 = in ? ous + (int64_t)k * NU17 + m : oxs + (int64_t)k * NX17 + OM;
+    *o2 = bad ? qnan : (in ? ou : ox8);
+    // dx' = [A|B] (dx, du)
+    const T zb = csel(m_in, du, dxs);
+    T acc = cr.c8s * dx8 + csel(m_in, dxs, T(0));
+    chain16(acc, zb, cr.ab);
+    const T acc8 = sum16(cr.ab8o * zb, cr.c88 * dx8);
+    dxs = acc;
+    dx8 = acc8;
+    load(k + FD < N ? k + FD : N - 1, cr);   // (unconditional refill, a clamped stage index)
+  };
+  int k0 = 0;
+  for (; k0 + FD <= N; k0 += FD) {
+    static_for<FD>([&](auto sl) { stage(k0 + decltype(sl)::value, ring[decltype(sl)::value]); });
+  }
+  static_for<FD>([&](auto sl) {
+    if (k0 + decltype(sl)::value < N) stage(k0 + decltype(sl)::value, ring[decltype(sl)::value]);
+  });
+  {   // the terminal stage: QN dx_N
+    w.DX[(int64_t)N * NX17 + s] = dxs;
+    w.DX[(int64_t)N * NX17 + OM] = dx8;
+    T wq[LN];
+#pragma unroll
+    for (int tp = 0; tp < LN; ++tp) wq[tp] = W.QN[s * NX17 + sown(tp)];
+    T ox = W.QN[s * NX17 + OM] * dx8;
+    chain16(ox, dxs, wq);
+    const T ox8 = sum16(W.QN[OM * NX17 + s] * dxs, W.QN[OM * NX17 + OM] * dx8);
+    oxs[(int64_t)N * NX17 + s] = bad ? qnan : ox;
+    oxs[(int64_t)N * NX17 + OM] = bad ? qnan : ox8;
+  }
+}
+
+// The weight gradients of one instance per workgroup, from the adjoint trajectory the forward
+// pass left in the workspace and the residuals rx_k = X_k - xref_k, ru_k = U_k - uref_k:
+//   gQ = -s sym(sum_{k<N} dx_k rx_k^T),  gR = -s sym(sum_{k<N} du_k ru_k^T),  gQN = -sym(dx_N rx_N^T).
+// A lane forms entry (r, c), c <= r, of a sum once and stores it to both places (bitwise
+// symmetric); the stage loop holds four loads and two FMAs, nothing indexed.
+template <class T>
+__global__ void __launch_bounds__(64) vjp17_w_kernel(Vjp17Args<T> a) {
+  const int64_t c = blockIdx.x;
+  const int64_t b = a.b0 + c;
+  const int N = a.N;
+  const WsV17<T> w(a.ws + c * vjp17_elems(N), N);
+  const bool bad = a.status[b] == MPCB_STATUS_NAN;
+  const T qnan = __builtin_nan("");
+  const T* Xp = a.X + b * (int64_t)(N + 1) * NX17;
+  const T* Up = a.U + b * (int64_t)N * NU17;
+  const T* xrp = a.xref + b * a.xref_sb;
+  const T* urp = a.uref + b * a.uref_sb;
+  constexpr int TQ = NX17 * (NX17 + 1) / 2, TR = NU17 * (NU17 + 1) / 2;
+  const T hs = T(-0.5) * a.s;
+  for (int e = threadIdx.x; e < TQ + TR; e += 64) {
+    const bool isq = e < TQ;
+    const int f = isq ? e : e - TQ;
+    int r = 0;
+    while ((r + 1) * (r + 2) / 2 <= f) ++r;   // row of the packed lower triangle
+    const int cc = f - r * (r + 1) / 2;
+    const int nd = isq ? NX17 : NU17;
+    const T* dz = isq ? w.DX : w.DU;
+    const T* zp = isq ? Xp : Up;
+    const T* rp = isq ? xrp : urp;
+    T s1 = T(0), s2 = T(0);
+    for (int k = 0; k < N; ++k) {
+      const int64_t o = (int64_t)k * nd;
+      s1 += dz[o + r] * (zp[o + cc] - rp[o + cc]);
+      s2 += dz[o + cc] * (zp[o + r] - rp[o + r]);
+    }
+    const T v = bad ? qnan : hs * (s1 + s2);
+    T* out = isq ? a.gQ : a.gR;
+    if (out) {
+      out[b * (int64_t)(nd * nd) + r * nd + cc] = v;
+      out[b * (int64_t)(nd * nd) + cc * nd + r] = v;
+    }
+    if (isq && a.gQN) {
+      const int64_t o = (int64_t)N * NX17;
+      const T vn = bad ? qnan
+                       : T(-0.5) * (w.DX[o + r] * (Xp[o + cc] - xrp[o + cc]) + w.DX[o + cc] * (Xp[o + r] - xrp[o + r]));
+      a.gQN[b * (int64_t)(NX17 * NX17) + r * NX17 + cc] = vn;
+      a.gQN[b * (int64_t)(NX17 * NX17) + cc * NX17 + r] = vn;
+    }
+  }
+}
+
 }  // namespace q17
 
 template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_t st) {
@@ -1371,5 +1788,15 @@ template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_
 }
 template hipError_t launch_riccati17q<double>(const FullArgs<double>&, hipStream_t);
 template hipError_t launch_riccati17q<float>(const FullArgs<float>&, hipStream_t);
+
+template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st) {
+  hipLaunchKernelGGL((q17::vjp17_lin_kernel<T>), dim3((unsigned)((a.nb * a.N + GQ17 - 1) / GQ17)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL((q17::vjp17_kernel<T>), dim3((unsigned)((a.nb + q17::GR - 1) / q17::GR)), dim3(64), 0, st, a);
+  if (a.gQ || a.gR || a.gQN)
+    hipLaunchKernelGGL((q17::vjp17_w_kernel<T>), dim3((unsigned)a.nb), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+template hipError_t launch_vjp17<double>(const Vjp17Args<double>&, hipStream_t);
+template hipError_t launch_vjp17<float>(const Vjp17Args<float>&, hipStream_t);
 
 }  // namespace mpcb

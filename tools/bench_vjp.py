@@ -17,7 +17,11 @@ them alike.  Prints one JSON line per shape.
 ``--weights`` adds mpcb_solve_vjp_w with all six outputs (X and U: the timed solve's) and its ratio
 to the plain product on the same build.
 
-    python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4] [--weights]
+``--full17`` times mpcb_solve_vjp17 instead (the 17/6 model at 4096 x N = 60, fp64, the shape of
+tools/bench_full17.py), with an empty and a half-full mask and, with ``--weights``, all six
+outputs, next to the unboxed mpcb_solve_iterate of the same handle.
+
+    python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4] [--weights] [--full17]
 """
 import argparse
 import json
@@ -123,6 +127,90 @@ def bench(name, runs, warmup, inner, weights=False):
     return out
 
 
+def bench_full17(runs, warmup, inner, weights=False, B=4096, N=60, dtype='f64'):
+    """mpcb_solve_vjp17 next to the unboxed mpcb_solve_iterate of the same handle: 4096 x N = 60,
+    fp64, the draws of tools/bench_full17.py (random x0 around hover, per-instance POC parameters).
+    A synthetic mask (about half of the components clamped) is timed as well: it costs what the
+    empty one costs, the mask being an operand of selects."""
+    import numpy as np
+    import torch
+
+    from mpc_blaster_amd import BatchedMPC, MPCConfig, _lib
+    rng = np.random.default_rng(1017)
+    x0 = np.zeros((B, 17))
+    x0[:, 0:3] = rng.uniform(-1, 1, (B, 3))
+    x0[:, 2] += 3.5
+    x0[:, 3:6] = rng.uniform(-0.17, 0.17, (B, 3))
+    x0[:, 6:9] = rng.uniform(-0.5, 0.5, (B, 3))
+    x0[:, 9:12] = rng.uniform(-0.087, 0.087, (B, 3))
+    xref = np.zeros((1, N + 1, 17))
+    xref[..., 2], xref[..., 14] = 3.5, 0.2
+    uref = np.zeros((1, N, 6))
+    uref[..., :4] = 22.0725
+    p = np.zeros((B, 25))
+    p[:, :24] = rng.uniform(-0.5, 0.5, (B, 24))
+    p[:, 24] = 2.2 * 9.81
+    cfg = MPCConfig.full(N=N, dtype=dtype)
+    m = BatchedMPC(cfg, max_batch=B)
+    dt, dev = cfg.torch_dtype, m._tdev
+    x0, xr, ur, pt = (torch.as_tensor(a, dtype=dt, device=dev) for a in (x0, xref, uref, p))
+    m.set_params(pt)
+    m.solve(x0, xr, ur)
+    xbar, ubar = m.get_state_trajectory().clone(), m.get_input_trajectory().clone()
+    gen = torch.Generator(device=dev).manual_seed(1017)
+    gX = torch.randn((B, N + 1, 17), dtype=dt, device=dev, generator=gen)
+    gU = torch.randn((B, N, 6), dtype=dt, device=dev, generator=gen)
+    fixed = (torch.rand((B, N, 6), device=dev, generator=gen) < 0.5).to(torch.uint8)
+    u0 = torch.empty((B, 6), dtype=dt, device=dev)
+    X, U = torch.empty_like(xbar), torch.empty_like(ubar)
+    gx0, gxr, gur = torch.empty((B, 17), dtype=dt, device=dev), torch.empty_like(xbar), torch.empty_like(ubar)
+    gQ, gR = torch.empty((B, 17, 17), dtype=dt, device=dev), torch.empty((B, 6, 6), dtype=dt, device=dev)
+    gQN = torch.empty_like(gQ)
+    sts = {k: torch.empty((B,), dtype=torch.int32, device=dev) for k in ('solve_iterate', 'vjp17', 'vjp17_masked', 'vjp17_w')}
+    P, null, st = m._ptr, m._ptr(None), m._stream()
+
+    def vjp_call(key, fx, wg):
+        w = (P(gQ), P(gR), P(gQN)) if wg else (null, null, null)
+        return lambda: _lib.check(m.lib.mpcb_solve_vjp17(
+            m._h, B, P(xbar), P(ubar), fx, P(X) if wg else null, P(U) if wg else null, P(xr) if wg else null, 0,
+            P(ur) if wg else null, 0, P(gX), P(gU), P(gx0), P(gxr), P(gur), *w, P(sts[key]), st))
+    variants = {
+        'solve_iterate': lambda: _lib.check(m.lib.mpcb_solve_iterate(
+            m._h, B, P(x0), 17, P(xbar), P(ubar), P(xr), 0, P(ur), 0, null, 0, P(u0), P(X), P(U),
+            P(sts['solve_iterate']), st)),
+        'vjp17': vjp_call('vjp17', null, False),
+        'vjp17_masked': vjp_call('vjp17_masked', P(fixed), False),
+    }
+    if weights:
+        variants['vjp17_w'] = vjp_call('vjp17_w', null, True)
+    for _ in range(warmup):
+        for f in variants.values():
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(runs):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) / inner)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = dict(shape='full17', B=B, N=N, dtype=dtype, box=False, runs=runs, inner=inner,
+               **{f'{k}_ms': round(v, 4) for k, v in med.items()},
+               **{f'{k}_min_ms': round(min(v), 4) for k, v in t.items()},
+               vjp17_over_solve=round(med['vjp17'] / med['solve_iterate'], 3),
+               vjp17_masked_over_solve=round(med['vjp17_masked'] / med['solve_iterate'], 3),
+               **{f'{k}_status_ok': int((sts[k] == 0).sum()) for k in variants})
+    if weights:
+        out.update(vjp17_w_over_solve=round(med['vjp17_w'] / med['solve_iterate'], 3),
+                   vjp17_w_over_vjp17=round(med['vjp17_w'] / med['vjp17'], 3))
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--runs', type=int, default=20)
@@ -131,7 +219,12 @@ def main():
     ap.add_argument('--shapes', default='c2,c3,c4')
     ap.add_argument('--weights', action='store_true',
                     help='also time mpcb_solve_vjp_w (the weight gradients gQ, gR, gQN in the same launch)')
+    ap.add_argument('--full17', action='store_true',
+                    help='time mpcb_solve_vjp17 (17/6 model, 4096 x N = 60, fp64) instead of the 12/4 shapes')
     a = ap.parse_args()
+    if a.full17:
+        bench_full17(a.runs, a.warmup, a.inner, a.weights)
+        return
     for name in a.shapes.split(','):
         bench(name, a.runs, a.warmup, a.inner, a.weights)
 
