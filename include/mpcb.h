@@ -13,7 +13,13 @@
  *    MPCB_E_* code; ``mpcb_last_error()`` gives a thread-local message.
  *  - Array arguments are DEVICE pointers (HBM, caller-owned, e.g. torch ROCm tensors) of the
  *    handle's dtype (double when cfg.dtype == MPCB_F64, float when MPCB_F32).  Per-instance
- *    strides are in ELEMENTS; a stride of 0 broadcasts one array to the whole batch.
+ *    strides are in ELEMENTS; a stride of 0 broadcasts one array to the whole batch.  A stride
+ *    may exceed the record's length (padded records); a negative stride is refused with
+ *    MPCB_E_INVALID by every entry point that takes one.
+ *  - Alignment: input arrays, u0, status and every other output need only the alignment of their
+ *    element type (8 bytes for double, 4 for float and int32), at the base and at every record;
+ *    the solves' X and U outputs alone must be 16-byte aligned.  A call writes nothing outside
+ *    the arrays it is given.
  *  - Calls are asynchronous on ``hip_stream`` (NULL = default stream).  The Python facade
  *    synchronises to keep acados' synchronous semantics.
  *  - A handle is bound to one device, owns its workspace, and is not re-entrant.

@@ -785,11 +785,19 @@ extern "C" int mpcb_last_timing(mpcb_handle* h, float* ms) {
   return MPCB_OK;
 }
 
-static int check_solve(mpcb_handle* h, int64_t B, const void* x0, const void* xref, const void* uref,
-                       const void* u0, const void* X, const void* U, const int32_t* status) {
+// Per-instance strides are element counts from the array's base: 0 broadcasts, negative is refused.
+static int check_strides(int64_t a, int64_t b = 0, int64_t c = 0, int64_t d = 0) {
+  if (a < 0 || b < 0 || c < 0 || d < 0) return fail(MPCB_E_INVALID, "negative stride");
+  return MPCB_OK;
+}
+
+static int check_solve(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xref,
+                       int64_t xref_sb, const void* uref, int64_t uref_sb, int64_t wind_sb, const void* u0,
+                       const void* X, const void* U, const int32_t* status) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (B < 0 || B > h->max_batch)
     return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_strides(x0_sb, xref_sb, uref_sb, wind_sb)) return rc;
   if (B > 0 && (!x0 || !xref || !uref || !u0 || !status))
     return fail(MPCB_E_INVALID, "x0, xref, uref, u0 and status are required");
   // the trajectory outputs are written in 16-byte chunks
@@ -801,7 +809,7 @@ static int check_solve(mpcb_handle* h, int64_t B, const void* x0, const void* xr
 extern "C" int mpcb_solve(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xref,
                int64_t xref_sb, const void* uref, int64_t uref_sb, const void* wind, int64_t wind_sb,
                void* u0, void* X, void* U, int32_t* status, void* stream) {
-  int rc = check_solve(h, B, x0, xref, uref, u0, X, U, status);
+  int rc = check_solve(h, B, x0, x0_sb, xref, xref_sb, uref, uref_sb, wind_sb, u0, X, U, status);
   if (!rc) rc = check_params(h, B);
   if (rc || B == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
@@ -816,7 +824,7 @@ extern "C" int mpcb_solve_iterate(mpcb_handle* h, int64_t B, const void* x0, int
                        const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
                        int64_t uref_sb, const void* wind, int64_t wind_sb, void* u0, void* X, void* U,
                        int32_t* status, void* stream) {
-  int rc = check_solve(h, B, x0, xref, uref, u0, X, U, status);
+  int rc = check_solve(h, B, x0, x0_sb, xref, xref_sb, uref, uref_sb, wind_sb, u0, X, U, status);
   if (!rc) rc = check_params(h, B);
   if (rc || B == 0) return rc;
   if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
@@ -832,6 +840,7 @@ extern "C" int mpcb_linearize(mpcb_handle* h, int64_t B, const void* xbar, const
                    int64_t wind_sb, void* A, void* Bm, void* xnext, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (B < 0) return fail(MPCB_E_INVALID, "negative batch");
+  if (int rc = check_strides(wind_sb)) return rc;
   if (B == 0) return MPCB_OK;
   if (!xbar || !ubar || !A || !Bm || !xnext) return fail(MPCB_E_INVALID, "null array");
   if (int rc = check_params(h, B)) return rc;
@@ -901,6 +910,7 @@ extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_s
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (B < 0 || B > h->max_batch)
     return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_strides(x0_sb, xref_sb, uref_sb, wind_sb)) return rc;
   if (!cost && !res_eq && !res_ineq && !res_stat) return fail(MPCB_E_INVALID, "no output requested");
   if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
   if (h->cfg.box_x && res_stat)
@@ -984,7 +994,7 @@ extern "C" int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B, const void* xbar, con
   if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
   if (wg && (!X || !U || !xref || !uref))
     return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
-  if (wg && (xref_sb < 0 || uref_sb < 0)) return fail(MPCB_E_INVALID, "negative reference stride");
+  if (int rc = check_strides(xref_sb, uref_sb, wind_sb)) return rc;
   HIP_TRY(hipSetDevice(h->device));
   if (h->cfg.dtype == MPCB_F64)
     return vjp_impl<double>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
@@ -1059,7 +1069,7 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
   if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
   if (wg && (!X || !U || !xref || !uref))
     return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
-  if (wg && (xref_sb < 0 || uref_sb < 0)) return fail(MPCB_E_INVALID, "negative reference stride");
+  if (int rc = check_strides(xref_sb, uref_sb)) return rc;
   if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
   if (h->cfg.dtype == MPCB_F64)
@@ -1073,6 +1083,7 @@ extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const voi
                   int64_t wind_sb, double T, void* x_out, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (B < 0) return fail(MPCB_E_INVALID, "negative batch");
+  if (int rc = check_strides(wind_sb)) return rc;
   if (B == 0) return MPCB_OK;
   if (!x || !u || !x_out) return fail(MPCB_E_INVALID, "null array");
   if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
@@ -1105,6 +1116,7 @@ extern "C" int mpcb_gen_inputs(mpcb_handle* h, int64_t B, uint64_t seed, uint64_
                     void* xref, int64_t xref_sb, void* uref, int64_t uref_sb, void* wind, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (B < 0) return fail(MPCB_E_INVALID, "negative batch");
+  if (int rc = check_strides(xref_sb, uref_sb)) return rc;
   if (B == 0) return MPCB_OK;
   if (!x0 || !xref || !uref) return fail(MPCB_E_INVALID, "null array");
   if (ref_kind == 1 && xref_sb == 0) return fail(MPCB_E_INVALID, "sinusoid refs need xref_sb > 0");

@@ -179,17 +179,23 @@ def _noise_move(o, inp, spec, trials=2, rel=2.0 ** -22):
     return worst
 
 
+def _accept_free(tag, o, u0, X, U, st, dtype, tol=None):
+    """The acceptance of an unconstrained 12/4 solve against its oracle ``o`` (shared with
+    tests/test_gpu_abi.py, which holds its baselines to the bounds of this file)."""
+    e = [relerr(u0, o['u0']).max(), relerr(X, o['X']).max(), relerr(U, o['U']).max()]
+    if tol is None:
+        tol = 1e-9 if dtype == 'f64' else 5e-5
+    print(f'{tag}: max rel err u0 {e[0]:.2e} X {e[1]:.2e} U {e[2]:.2e} (bound {tol:.1e})')
+    assert (st == o['status']).all() and (st == 0).all()
+    assert max(e) < tol
+
+
 def _check_free(path, N, B, mode, alt, dtype, monkeypatch, tol=None):
     o, spec = _oracle(N, B, mode, alt, dtype, False)
     m = _handle(path, N, B, dtype, monkeypatch, **ac.fields(alt=alt, box='none', dtype=dtype))
     u0, X, U, st = _solve12(m, N, B, mode, alt, dtype)
     _kernels_are(m, B, mode, PATHS[path][2](dtype, _it(mode)))
-    e = [relerr(u0, o['u0']).max(), relerr(X, o['X']).max(), relerr(U, o['U']).max()]
-    if tol is None:
-        tol = 1e-9 if dtype == 'f64' else 5e-5
-    print(f'ALT-{alt} {path} {dtype} N={N} {mode}: max rel err u0 {e[0]:.2e} X {e[1]:.2e} U {e[2]:.2e} (bound {tol:.1e})')
-    assert (st == o['status']).all() and (st == 0).all()
-    assert max(e) < tol
+    _accept_free(f'ALT-{alt} {path} {dtype} N={N} {mode}', o, u0, X, U, st, dtype, tol)
 
 
 @pytest.mark.parametrize('alt', ALTS)
@@ -260,8 +266,16 @@ def _check_box(path, N, B, mode, alt, dtype, monkeypatch, max_as_iter=200, group
     if 'model' not in groups and 'riccati' in expected:   # the default diagonal inertia's instantiation
         expected['riccati'] = expected['riccati'].replace(', false>', ', true>')
     _kernels_are(m, B, mode, expected)
+    _accept_box(f'ALT-{alt} {path} {dtype} N={N} {mode}', o, spec, inp, u0, X, U, st, dtype)
+
+
+def _accept_box(tag, o, spec, inp, u0, X, U, st, dtype):
+    """The acceptance of a 12/4 input-box solve against its oracle ``o`` (shared with
+    tests/test_gpu_abi.py)."""
+    from test_gpu_fuzz import qp_objective
+    B = u0.shape[0]
     eu, ex, eU = relerr(u0, o['u0']), relerr(X, o['X']), relerr(U, o['U'])
-    print(f'ALT-{alt} {path} {dtype} N={N} {mode}: max rel err u0 {eu.max():.2e} X {ex.max():.2e} U {eU.max():.2e}')
+    print(f'{tag}: max rel err u0 {eu.max():.2e} X {ex.max():.2e} U {eU.max():.2e}')
     assert (st == o['status']).all() and (st == 0).all()
     tb = 1e-6 if dtype == 'f64' else 2e-4
     assert (U >= spec.lbu - tb).all() and (U <= spec.ubu + tb).all()
@@ -490,8 +504,15 @@ def test_full17_matches_oracle(bounds, dtype, N, mode, alt):
                  'linearise': f'mpcb::lin17ws_kernel<{T[dtype]}>'}
     u0, X, U, st = (t.cpu().numpy() for t in (m.get_control(), m.get_state_trajectory(),
                                                m.get_input_trajectory(), m.get_status()))
+    _accept17(f'17/6 ALT-{alt} {bounds} {dtype} N={N} {mode}', o, spec, x0, xref, uref, u0, X, U, st, bounds, dtype)
+
+
+def _accept17(tag, o, spec, x0, xref, uref, u0, X, U, st, bounds, dtype):
+    """The acceptance of a 17/6 solve against its oracle ``o`` (shared with tests/test_gpu_abi.py)."""
+    from test_gpu_fuzz17 import qp_objective
+    N = spec.N
     e = [relerr(u0, o['u0']).max(), relerr(X, o['X']).max(), relerr(U, o['U']).max()]
-    print(f'17/6 ALT-{alt} {bounds} {dtype} N={N} {mode}: rel err u0 {e[0]:.2e} X {e[1]:.2e} U {e[2]:.2e}, '
+    print(f'{tag}: rel err u0 {e[0]:.2e} X {e[1]:.2e} U {e[2]:.2e}, '
           f'status {np.bincount(st, minlength=5).tolist()}')
     assert (st == o['status']).all()
     if bounds == 'none':
