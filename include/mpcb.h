@@ -324,6 +324,53 @@ int mpcb_solve_vjp17(mpcb_handle* h, int64_t B,
                      int32_t* status, void* hip_stream);
 
 /*
+ * The local feedback law and the cost-to-go Hessian of the SQP_RTI step, on both models and in
+ * both dtypes.  The call works on the LQ problem that mpcb_solve_iterate solves at (xbar, ubar),
+ * with the handle's weights, model, wind (12/4) or parameters (17/6) and s = cfg.cost_scale:
+ *   P_N = QN;  for k = N-1 .. 0, [A_k | B_k] the exact RK4 sensitivities at (xbar_k, ubar_k):
+ *     H   = blkdiag(s Q, s R) + [A|B]^T P_{k+1} [A|B]
+ *     H~  = H with the clamped input components masked: their rows and columns of H_uu zeroed and
+ *           its diagonal set to 1 there, their rows of H_ux zeroed
+ *     K_k = -H~uu^-1 H~ux                    (a clamped component's row is exactly 0, bitwise)
+ *     P_k = H_xx + H_ux^T K_k                (the unmasked H_ux)
+ * No gap, reference or linear term enters: neither K nor P depends on them.
+ *   K  [B,N,nu,nx]   row-major, of the handle's dtype (acados: get_from_qp_in(k, 'K'))
+ *   P0 [B,nx,nx]     P_0, bitwise symmetric             (acados: get_from_qp_in(0, 'P'))
+ *   either may be NULL, not both; all arrays are contiguous; K and P0 need only element alignment;
+ *   nothing outside K, P0 and status is written
+ * What they mean.  On a fixed active set, in iterate mode, two solves that differ only in x0
+ * return (X, U) and (X', U') with
+ *   U'_k - U_k = K_k (X'_k - X_k)   for every k,   in particular  d u0 / d x0 = K_0,
+ * which is the feedback u = U_j + K_j (x_meas - X_j) an RTI deployment applies between solves, and
+ * the optimal value V of the solve's QP as a function of x0 satisfies
+ *   V(x0 + d) + V(x0 - d) - 2 V(x0) = d^T P_0 d:   P_0 is the Hessian of the value function.
+ * The active set:
+ *   fixed [B,N,nu] uint8   nonzero = component (k, m) is clamped; accepted on both models, and the
+ *                          result is exact for the mask it is given.  A stage with every component
+ *                          clamped is valid (K_k = 0, P_k = H_xx).  On the 12/4 model the kernel
+ *                          keeps one mask word per input, so `fixed` needs N <= 64 (the limit
+ *                          mpcb_create sets for box_u there): MPCB_E_UNSUPPORTED beyond it.  The
+ *                          17/6 model has no such limit.
+ *   fixed == NULL          12/4 handle with the input box: U [B,N,nu] is required and the set is
+ *                          read from it by the rule of mpcb_solve_vjp (on or beyond a bound);
+ *                          12/4 handle without the box, or a 17/6 handle: nothing is clamped and U
+ *                          is not read (the 17/6 caller derives `fixed`, see mpcb_solve_vjp17)
+ * status[B]: MPCB_STATUS_OK; MPCB_STATUS_NAN for an instance with a non-finite xbar, ubar, wind,
+ * parameter, or U where U is read (its outputs are all NaN, other instances keep their bits);
+ * MPCB_STATUS_QP_FAIL when a masked input Hessian is not positive definite.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle with box_x (the reason given at mpcb_solve_vjp17), for
+ * wind on a 17/6 handle and for fixed on a 12/4 handle with N > 64.  MPCB_E_INVALID: both outputs NULL, B > max_batch, a negative stride, a
+ * 12/4 input-box handle with neither U nor fixed.  The workspace is allocated by the first call
+ * (MPCB_E_NOMEM) and is not counted by mpcb_workspace_bytes; on the 17/6 model it is
+ * mpcb_solve_vjp17's, and large batches run in the chunks of the handle's solves.
+ */
+int mpcb_solve_gains(mpcb_handle* h, int64_t B,
+                     const void* xbar, const void* ubar,
+                     const void* U, const uint8_t* fixed,
+                     const void* wind, int64_t wind_sb,
+                     void* K, void* P0, int32_t* status, void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */

@@ -289,6 +289,11 @@ class BatchedMPC:
                              dtype=self.dtype, device=self._tdev)
         return ((U <= lb + active_tol) | (U >= ub - active_tol)).to(torch.uint8).contiguous()
 
+    def active_mask(self, U, active_tol=None):
+        """The active set of ``U`` [B,N,nu] by tolerance on either model (``active_mask17``'s rule
+        and defaults; that name is kept for the 17/6 callers)."""
+        return self.active_mask17(U, active_tol)
+
     def _solve_iterate_vjp17(self, xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed, active_tol):
         torch = _torch()
         if wind is not None:
@@ -336,6 +341,62 @@ class BatchedMPC:
             self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']), self._ptr(out['gxref']),
             self._ptr(out['guref']), self._ptr(out.get('gQ')), self._ptr(out.get('gR')),
             self._ptr(out.get('gQN')), self._ptr(out['status']), self._stream()))
+        return out
+
+    def solve_iterate_gains(self, xbar, ubar, U=None, fixed=None, active_tol=None, wind=None,
+                            want_K=True, want_P0=True):
+        """Feedback gains and cost-to-go Hessian of the ``solve_iterate`` step at (xbar, ubar)
+        (mpcb_solve_gains; include/mpcb.h has the recursion): a dict of device tensors ``K``
+        [B,N,nu,nx] (``U'_k - U_k = K_k (X'_k - X_k)`` between two solves that differ in x0 on one
+        active set; ``K[:, 0]`` is du0/dx0), ``P0`` [B,nx,nx] (the Hessian of the QP's optimal
+        value in x0, bitwise symmetric), ``status`` [B] (int32) and ``fixed``, the mask used (None
+        where the library read the set from ``U`` or nothing is clamped).  ``want_K`` /
+        ``want_P0`` = False leaves that output out (None), not both.  Asynchronous.
+
+        The active set.  ``fixed`` is a bool / uint8 tensor [B,N,nu], nonzero = clamped, on both
+        models.  Without it, ``active_tol`` with ``U`` builds the mask
+        ``(U <= lbu + active_tol) | (U >= ubu - active_tol)`` on an input-box handle; on a 12/4
+        input-box handle ``U`` alone has the library read the set by the rule of
+        ``solve_iterate_vjp`` (on or beyond a bound; required there when there is no mask), which
+        misses an instance the active set handed to the interior point: a tolerance finds it.  On
+        17/6 ``U`` alone uses the default tolerance of ``solve_iterate_vjp`` (1e-6 on f64,
+        required on f32).  Without ``fixed`` and ``U`` nothing is clamped.  A mask on a 12/4 handle
+        needs N <= 64 (``MpcbError``, MPCB_E_UNSUPPORTED); 17/6 has no such limit."""
+        torch = _torch()
+        if not want_K and not want_P0:
+            raise ValueError('solve_iterate_gains: want_K and want_P0 are both False')
+        if self.nx == 17 and wind is not None:
+            raise _lib.MpcbError('mpcb error -4: wind is a 12/4-model extension')
+        if active_tol is not None and U is None and fixed is None:
+            raise ValueError('active_tol needs U (the solve\'s output) to build the mask from')
+        N = self.cfg.N
+        xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar')
+        B = xb.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        ub, _ = self._dev(ubar, (N, self.nu), 'ubar', B)
+        Ud = None if U is None else self._dev(U, (N, self.nu), 'U', B)[0]
+        wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
+        dev = self._tdev
+        if fixed is not None:
+            if isinstance(fixed, np.ndarray) and not fixed.flags.writeable:
+                fixed = fixed.copy()   # torch.as_tensor warns on read-only arrays
+            fx = torch.as_tensor(fixed, device=dev)
+            if tuple(fx.shape) != (B, N, self.nu):
+                raise ValueError(f'fixed: expected shape [{B}, {N}, {self.nu}], got {tuple(fx.shape)}')
+            fx = (fx != 0).to(torch.uint8).contiguous()
+        elif Ud is not None and (self.nx == 17 or active_tol is not None):
+            fx = self.active_mask(Ud, active_tol)
+        else:
+            fx = None
+        out = dict(K=torch.empty((B, N, self.nu, self.nx), dtype=self.dtype, device=dev) if want_K else None,
+                   P0=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev) if want_P0 else None,
+                   status=torch.empty((B,), dtype=torch.int32, device=dev), fixed=fx)
+        self._keep_gains = (xb, ub, Ud, fx, wd)
+        _lib.check(self.lib.mpcb_solve_gains(
+            self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Ud if fx is None else None), self._ptr(fx),
+            self._ptr(wd), wd_sb, self._ptr(out['K']), self._ptr(out['P0']), self._ptr(out['status']),
+            self._stream()))
         return out
 
     def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,

@@ -11,13 +11,35 @@ from .api import BatchedMPC
 
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
-                xbar=None, ubar=None, diagnostics=False):
+                xbar=None, ubar=None, diagnostics=False, resolve_every: int = 1, feedback: bool = False,
+                active_tol=None):
     """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
+
+    ``resolve_every = h > 1`` (h <= N) models a controller slower than the plant: the solve runs
+    on the steps i = 0, h, 2h, ... from the persistent iterate and its trajectories (Xp, Up) are
+    kept; step i applies ``Up[:, j]``, j = i mod h, and with ``feedback=True`` the RTI feedback law
+    ``Up[:, j] + K[:, j] (x - Xp[:, j])`` with the gains of that solve
+    (``BatchedMPC.solve_iterate_gains`` at the iterate the solve started from, on the active set of
+    its U), clipped to the input box on a handle that has one.  ``active_tol`` is that call's
+    active-set tolerance: required with ``feedback`` on an f32 17/6 input-box handle, which has no
+    default (checked before the loop starts), optional elsewhere.  With the defaults every step
+    solves, as before.
 
     ``diagnostics=True`` evaluates the new iterate after each solve (``BatchedMPC.evaluate`` with
     that step's x0) and returns a fourth value: a dict of [B, nsim] tensors ``cost``, ``res_eq``,
     ``res_stat`` (without ``res_stat`` on a handle with a state box)."""
     import torch
+    h = int(resolve_every)
+    if h < 1 or h > mpc.cfg.N:
+        raise ValueError(f'resolve_every = {resolve_every}: expected 1 <= resolve_every <= N = {mpc.cfg.N}')
+    if h > 1 or feedback:
+        if diagnostics:
+            raise ValueError('diagnostics evaluates every step\'s solve: use resolve_every=1, feedback=False')
+        if feedback and active_tol is None and mpc.nx == 17 and mpc.cfg.boxed and mpc.cfg.dtype != 'f64':
+            raise ValueError('feedback=True on an f32 17/6 input-box handle needs active_tol (solve_iterate_gains)')
+        return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol)
+    if active_tol is not None:
+        raise ValueError('active_tol belongs to feedback=True')
     dev = f'cuda:{mpc.device}'
     dt = mpc.dtype
     x = torch.as_tensor(x0, dtype=dt, device=dev).contiguous()
@@ -48,4 +70,54 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
         Xs[:, i + 1] = x
     if diagnostics:
         return Xs, Us, worst, diag
+    return Xs, Us, worst
+
+
+def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol):
+    """closed_loop with a solve every h plant steps and, optionally, the feedback law between."""
+    import numpy as np
+    import torch
+    dev = f'cuda:{mpc.device}'
+    dt = mpc.dtype
+    x = torch.as_tensor(x0, dtype=dt, device=dev).contiguous()
+    B, N = x.shape[0], mpc.cfg.N
+    NX, NU = mpc.nx, mpc.nu
+    xb = torch.zeros((B, N + 1, NX), dtype=dt, device=dev) if xbar is None else \
+        torch.as_tensor(xbar, dtype=dt, device=dev).clone()
+    ub = torch.zeros((B, N, NU), dtype=dt, device=dev) if ubar is None else \
+        torch.as_tensor(ubar, dtype=dt, device=dev).clone()
+    u0 = torch.empty((B, NU), dtype=dt, device=dev)
+    st = torch.empty((B,), dtype=torch.int32, device=dev)
+    worst = torch.zeros((B,), dtype=torch.int32, device=dev)
+    Xs = torch.empty((B, nsim + 1, NX), dtype=dt, device=dev)
+    Us = torch.empty((B, nsim, NU), dtype=dt, device=dev)
+    Xs[:, 0] = x
+    box = mpc.cfg.boxed
+    if box:
+        lb = torch.as_tensor(np.broadcast_to(np.asarray(mpc.cfg.lbu, dtype=np.float64), (NU,)).copy(),
+                             dtype=dt, device=dev)
+        hb = torch.as_tensor(np.broadcast_to(np.asarray(mpc.cfg.ubu, dtype=np.float64), (NU,)).copy(),
+                             dtype=dt, device=dev)
+    K = None
+    for i in range(nsim):
+        j = i % h
+        if j == 0:
+            if feedback:
+                xb0, ub0 = xb.clone(), ub.clone()   # the solve overwrites the iterate in place
+            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st))
+            worst = torch.maximum(worst, st)
+            if feedback:
+                g = mpc.solve_iterate_gains(xb0, ub0, U=ub if box else None, wind=wind, want_P0=False,
+                                            active_tol=active_tol if box else None)
+                worst = torch.maximum(worst, g['status'])
+                K = g['K']
+        u = ub[:, j]
+        if feedback:
+            u = u + torch.einsum('bmi,bi->bm', K[:, j], x - xb[:, j])
+        if box:
+            u = torch.minimum(torch.maximum(u, lb), hb)
+        u = u.contiguous()
+        Us[:, i] = u
+        x = mpc.sim_step(x, u, T=plant_T, wind=wind)
+        Xs[:, i + 1] = x
     return Xs, Us, worst

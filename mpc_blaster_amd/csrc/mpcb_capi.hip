@@ -15,6 +15,7 @@
 #include "mpcb_full.h"
 #include "mpcb_kernels.h"
 #include "mpcb_vjp.h"
+#include "mpcb_gains.h"
 
 using namespace mpcb;
 
@@ -102,6 +103,8 @@ struct mpcb_handle {
   void* vjp_scratch = nullptr;   // mpcb_solve_vjp's slot workspace: allocated by its first call, not
                                  // counted in scratch_bytes
   int vjp_grid = 0;              // ... and its resident slots
+  void* gains_scratch = nullptr; // mpcb_solve_gains' slot workspace (12/4): allocated by its first call,
+  int gains_grid = 0;            // ... its resident slots; the 17/6 model uses vjp17_scratch
   void* vjp17_scratch = nullptr; // mpcb_solve_vjp17's chunk workspace: allocated by its first call, not
                                  // counted in scratch_bytes
 };
@@ -504,6 +507,7 @@ extern "C" int mpcb_destroy(mpcb_handle* h) {
   if (h->u_scratch) (void)hipFree(h->u_scratch);
   if (h->vjp_scratch) (void)hipFree(h->vjp_scratch);
   if (h->vjp17_scratch) (void)hipFree(h->vjp17_scratch);
+  if (h->gains_scratch) (void)hipFree(h->gains_scratch);
   delete h;
   return MPCB_OK;
 }
@@ -1011,20 +1015,27 @@ extern "C" int mpcb_solve_vjp(mpcb_handle* h, int64_t B, const void* xbar, const
                           gxref, guref, nullptr, nullptr, nullptr, status, stream);
 }
 
+// The chunk workspace that mpcb_solve_vjp17 and the 17/6 mpcb_solve_gains share (WsV17's carve):
+// one chunk of the handle's 17/6 solves, in whole wavefronts, allocated by the first call of either.
+template <class T>
+static int ensure_vjp17_ws(mpcb_handle* h) {
+  if (h->vjp17_scratch) return MPCB_OK;
+  const size_t bytes = (size_t)vjp17_elems(h->cfg.N) * sizeof(T) * (size_t)((h->chunk + 3) / 4 * 4);
+  const hipError_t e = hipMalloc(&h->vjp17_scratch, bytes);
+  if (e != hipSuccess) {
+    h->vjp17_scratch = nullptr;
+    return fail(MPCB_E_NOMEM, "vjp17 workspace %zu bytes: %s", bytes, hipGetErrorString(e));
+  }
+  return MPCB_OK;
+}
+
 template <class T>
 static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const uint8_t* fixed,
                       const void* X, const void* U, const void* xref, int64_t xref_sb, const void* uref,
                       int64_t uref_sb, const void* gX, const void* gU, void* gx0, void* gxref, void* guref,
                       void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
   const int N = h->cfg.N;
-  if (!h->vjp17_scratch) {   // one chunk of the handle's 17/6 solves, in whole wavefronts
-    const size_t bytes = (size_t)vjp17_elems(N) * sizeof(T) * (size_t)((h->chunk + 3) / 4 * 4);
-    const hipError_t e = hipMalloc(&h->vjp17_scratch, bytes);
-    if (e != hipSuccess) {
-      h->vjp17_scratch = nullptr;
-      return fail(MPCB_E_NOMEM, "vjp17 workspace %zu bytes: %s", bytes, hipGetErrorString(e));
-    }
-  }
+  if (int rc = ensure_vjp17_ws<T>(h)) return rc;
   Vjp17Args<T> a;
   a.N = N;
   a.h = (T)h->cfg.dt;
@@ -1077,6 +1088,107 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
                               guref, gQ, gR, gQN, status, stream);
   return vjp17_impl<float>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref,
                            guref, gQ, gR, gQN, status, stream);
+}
+
+template <class T>
+static int gains_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                      const uint8_t* fixed, const void* wind, int64_t wind_sb, void* K, void* P0,
+                      int32_t* status, void* stream) {
+  const int64_t slot = gains_slot_elems(h->cfg.N);
+  if (!h->gains_scratch) {
+    // resident slots: mpcb_solve_vjp's count (registers: <= 2 waves per SIMD)
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    int64_t grid = (int64_t)cus * 8;
+    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
+    // MPCB_GAINS_SLOTS: fewer slots, so that a small batch strides over them (tests)
+    if (const char* e = getenv("MPCB_GAINS_SLOTS"))
+      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
+    if (grid > waves) grid = waves;
+    if (grid < 1) grid = 1;
+    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
+    const hipError_t e = hipMalloc(&h->gains_scratch, bytes);
+    if (e != hipSuccess) {
+      h->gains_scratch = nullptr;
+      return fail(MPCB_E_NOMEM, "gains workspace %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    h->gains_grid = (int)grid;
+  }
+  GainsArgs<T> a;
+  a.B = B;
+  a.N = h->cfg.N;
+  a.mask = (fixed || h->cfg.box_u) ? 1 : 0;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = (const Weights<T>*)h->weights;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar; a.U = (const T*)U;
+  a.fixed = fixed;
+  a.wind = (const T*)wind; a.wind_sb = wind_sb;
+  a.K = (T*)K; a.P0 = (T*)P0;
+  a.status = status;
+  a.scratch = (T*)h->gains_scratch;
+  a.slot_elems = slot;
+  int64_t grid = (B + GROUPS - 1) / GROUPS;
+  if (grid > h->gains_grid) grid = h->gains_grid;
+  const hipError_t e = launch_gains<T>(a, (int)grid, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "gains launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+template <class T>
+static int gains17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const uint8_t* fixed,
+                        void* K, void* P0, int32_t* status, void* stream) {
+  if (int rc = ensure_vjp17_ws<T>(h)) return rc;
+  Gains17Args<T> g{};   // (no cotangents, references or product outputs: all null)
+  Vjp17Args<T>& a = g.v;
+  a.N = h->cfg.N;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
+  a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
+  a.fixed = fixed;
+  a.status = status;
+  a.ws = (T*)h->vjp17_scratch;
+  g.K = (T*)K; g.P0 = (T*)P0;
+  for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
+    a.b0 = b0;
+    a.nb = (B - b0 < h->chunk) ? B - b0 : h->chunk;
+    const hipError_t e = launch_gains17<T>(g, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MPCB_E_HIP, "gains17 launch: %s", hipGetErrorString(e));
+  }
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_gains(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                                const uint8_t* fixed, const void* wind, int64_t wind_sb, void* K, void* P0,
+                                int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full && h->cfg.box_x)
+    return fail(MPCB_E_UNSUPPORTED, "the gains do not cover the state box (active state rows)");
+  if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (!K && !P0) return fail(MPCB_E_INVALID, "no output requested");
+  if (!h->full && fixed && h->cfg.N > 64)
+    return fail(MPCB_E_UNSUPPORTED, "fixed needs N <= 64 on the 12/4 model (N=%d): one mask word per input", h->cfg.N);
+  if (!h->full && h->cfg.box_u && !U && !fixed)
+    return fail(MPCB_E_INVALID, "U or fixed is required on an input-box handle (the active set)");
+  if (int rc = check_strides(wind_sb)) return rc;
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (h->full)
+    if (int rc = check_params(h, B)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->full) {
+    if (h->cfg.dtype == MPCB_F64) return gains17_impl<double>(h, B, xbar, ubar, fixed, K, P0, status, stream);
+    return gains17_impl<float>(h, B, xbar, ubar, fixed, K, P0, status, stream);
+  }
+  if (h->cfg.dtype == MPCB_F64)
+    return gains_impl<double>(h, B, xbar, ubar, U, fixed, wind, wind_sb, K, P0, status, stream);
+  return gains_impl<float>(h, B, xbar, ubar, U, fixed, wind, wind_sb, K, P0, status, stream);
 }
 
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,

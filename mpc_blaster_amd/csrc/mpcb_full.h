@@ -470,6 +470,16 @@ struct WsV17 {
 };
 template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st);
 
+// ---- mpcb_solve_gains on the 17/6 model (mpcb_r17.hip): the linearisation kernel of the product
+// above, on its workspace, then the backward pass that stores K_k and P_0.  Of `v` the chunk, the
+// model, the weights, the parameters, (xbar, ubar), fixed, status and ws are read.
+template <class T>
+struct Gains17Args {
+  Vjp17Args<T> v;
+  T* K; T* P0;       // [B][N][6][17], [B][17][17], either nullable
+};
+template <class T> hipError_t launch_gains17(const Gains17Args<T>& a, hipStream_t st);
+
 // ev (nullable): 4 events recorded before nominal17, after it, after lin17ws and after riccati17.
 template <class T> hipError_t launch_full17(const FullArgs<T>& a, hipStream_t st, hipEvent_t* ev = nullptr);
 template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_t st);

@@ -1774,6 +1774,227 @@ __global__ void __launch_bounds__(64) vjp17_w_kernel(Vjp17Args<T> a) {
   }
 }
 
+// ---- mpcb_solve_gains on the 17/6 model: the feedback gains K_k and the cost-to-go Hessian P_0 --
+// Runs after vjp17_lin_kernel on the same workspace.  vjp17_kernel's backward pass without any
+// linear term (no cotangents, no p, no h_u, no k): Y = P [A|B]_z, G = [A|B]^T Y, the 6x6 system
+// masked by the stage's six mask bits, K_k = -H~uu^-1 H~ux stored straight to K [B,N,6,17], then
+// P_0 [B,17,17] from the lanes' columns.  Entry (i, s) of P comes from one lane for both places
+// (the symmetric exchange), and state 8's column is stored as the lanes' row entries, so P_0 is
+// bitwise symmetric.  Every input was read by the linearisation, whose check values decide the NaN
+// rule before the first store.  Stores carry no lane-divergent branch: an output nobody asked for
+// and a padding group's go to the group's own workspace slot (the gains to KR, P_0 over [A|B],
+// which is read no more by then).
+template <class T>
+struct PreG {
+  T ab[NX17];      // column z of [A_k | B_k]
+  T a8[5];         // the nonzeros of the implicit column 8
+  uint8_t fx;      // the mask byte of input m (input lanes)
+};
+
+template <class T>
+__global__ void __launch_bounds__(64) gains17_kernel(Gains17Args<T> ga) {
+  __shared__ Lds<T> lds_all[GR];
+  __shared__ T sQ[NX17 * NX17];
+  __shared__ T sR[NU17 * NU17];
+  const Vjp17Args<T>& a = ga.v;
+  // fp64: the kernel fits the 256 architectural registers exactly, which admits two waves per SIMD,
+  // and a chunk of 4096 instances is 1024 one-wave workgroups on 1024 SIMDs: two of them sharing a
+  // SIMD while another idles cost more than a tenth of the kernel's time.  One accumulation register
+  // counted as used puts the allocation above half of the file, one wave per SIMD, as
+  // vjp17_kernel<double> (256 + 2) runs.
+  if constexpr (sizeof(T) == 8) asm volatile("" ::: "a0");
+  const int lane = threadIdx.x;
+  const int qi = lane / LN;
+  const int t = lane % LN;
+  const int64_t c = (int64_t)blockIdx.x * GR + qi;
+  const bool valid = c < a.nb;
+  // (a ragged last wave's extra groups: vjp17_kernel's note)
+  const int64_t b = a.b0 + (valid ? c : a.nb - 1);
+  const int N = a.N;
+  const Weights17<T>& W = *a.W;
+  const bool in = t >= 8 && t < 14;
+  const int s = sown(t);
+  const int z = zcol(t);
+  const int m = in ? t - 8 : 0;
+  for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
+  for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  __syncthreads();
+  const WsV17<T> w(a.ws + c * vjp17_elems(N), N);
+  Lds<T>& L = lds_all[qi];
+  constexpr int KR_N = Ws17<T>::KR_N;
+  constexpr int KN = NU17 * NX17;
+  static_assert(KR_N >= KN, "the gains' sink is the workspace's KR block");
+  const uint64_t m_in = lane_mask(in);
+  const bool hasF = a.fixed != nullptr;
+  const uint8_t* fxp = hasF ? a.fixed + b * (int64_t)N * NU17 : reinterpret_cast<const uint8_t*>(w.AB);
+  const bool outK = valid && ga.K, outP = valid && ga.P0;
+  T* const kbase = outK ? ga.K + b * (int64_t)N * KN : w.KR;
+  const int64_t kst = outK ? KN : KR_N;
+  T* const pbase = outP ? ga.P0 + b * (int64_t)(NX17 * NX17) : w.AB;
+
+  // ---- the NaN rule: the linearisation's stage values
+  T chk = T(0);
+  for (int k = t; k < N; k += LN) chk += w.CK[k];
+  chk = sum16(chk);
+  const bool bad = chk != chk;
+  const T qnan = __builtin_nan("");
+
+  // ---- backward: P_N = QN
+  T Pc[NX17], P88;
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) Pc[i] = W.QN[i * NX17 + s];
+  P88 = W.QN[OM * NX17 + OM];
+  auto prefetch = [&](int k, PreG<T>& p) {
+    const T* ABk = w.AB + (int64_t)k * NZ17 * NX17;
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) p.ab[i] = ABk[z * NX17 + i];
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) p.a8[r5] = ABk[OM * NX17 + c8row(r5)];
+    p.fx = fxp[(int64_t)k * NU17 + m];
+  };
+  bool qp_ok = true;
+  PreG<T> nx;
+  prefetch(N - 1, nx);
+  for (int k = N - 1; k >= 0; --k) {
+    const PreG<T> cu = nx;
+    prefetch(k > 0 ? k - 1 : 0, nx);   // (unconditional: no branch join on the loads)
+    // the stage's six mask bits: the input lanes' bytes meet in a ballot, bit 16 qi + 8 + n
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(hasF && cu.fx != 0);
+    const unsigned fm = (unsigned)(bal >> (qi * LN + 8)) & 63u;
+    uint64_t mf[NU17];
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) mf[n] = lane_mask(((fm >> n) & 1u) != 0);
+    // ---- Y = P [A|B]_z (bc18's vector slot is not used: there is no linear term)
+    T y[NX17], hab = T(0);
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) y[i] = T(0);
+    static_for<LN>([&](auto l) {
+      constexpr int tl = decltype(l)::value;
+      bc18<tl>(y, hab, Pc, T(0), cu.ab[sown(tl)]);
+    });
+    diag16_sown(y, Pc[OM], cu.ab[OM]);
+    y[OM] += P88 * cu.ab[OM];
+    // ---- G_z = [A|B]^T Y_z
+    T g[LN];
+#pragma unroll
+    for (int i = 0; i < LN; ++i) g[i] = T(0);
+#pragma unroll
+    for (int l = 0; l < NX17; ++l) diag16(g, cu.ab[l], y[l]);
+    T g8 = T(0);
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) g8 += cu.a8[r5] * y[c8row(r5)];
+#pragma unroll
+    for (int ci = 0; ci < 6; ++ci) L.YC[ci][t] = y[ids(ci)];
+    wave_lds_sync();
+    // ---- input lanes: their column G[:, 17+m] + s R -> Huu, Hux[:, 8]
+    if (in) {
+#pragma unroll
+      for (int n = 0; n < NU17; ++n) L.HU[m][n] = g[8 + n] + sR[n * NU17 + m];
+      L.HU[m][7] = g8;
+    }
+    wave_lds_sync();
+    // ---- this lane's state column Gs = G[:, s] (23 rows by z index)
+    T Gs[NZ17];
+    {
+      const int ci = in ? m : 0;
+      T spc = T(0);
+#pragma unroll
+      for (int r5 = 0; r5 < 5; ++r5) spc += cu.a8[r5] * Pc[c8row(r5)];
+#pragma unroll
+      for (int tp = 0; tp < LN; ++tp) Gs[zcol(tp)] = csel(m_in, L.YC[ci][tp], g[tp]);
+#pragma unroll
+      for (int r6 = 0; r6 < 6; ++r6) Gs[ids(r6)] = csel(m_in, Pc[ids(r6)], y[ids(r6)]);
+      Gs[OM] = csel(m_in, spc, g8);
+    }
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) Gs[i] += sQ[i * NX17 + xpos(s)];
+    T spc_own = T(0);
+#pragma unroll
+    for (int r5 = 0; r5 < 5; ++r5) spc_own += cu.a8[r5] * Pc[c8row(r5)];   // (P a)_s
+    T pa8 = P88 * cu.a8[0];                                                // (P a)_8
+    T G88;
+    {
+      const T pc8 = Pc[OM];
+      pa8 += bcast<tstate(2)>(pc8) * cu.a8[1] + bcast<tstate(14)>(pc8) * cu.a8[2] +
+             bcast<tstate(15)>(pc8) * cu.a8[3] + bcast<tstate(16)>(pc8) * cu.a8[4];
+      G88 = cu.a8[0] * pa8 + cu.a8[1] * bcast<tstate(2)>(spc_own) + cu.a8[2] * bcast<tstate(14)>(spc_own) +
+            cu.a8[3] * bcast<tstate(15)>(spc_own) + cu.a8[4] * bcast<tstate(16)>(spc_own);
+      G88 += sQ[OM * NX17 + xpos(OM)];
+    }
+    // ---- Huu masked (oracle.ocp._masked_stage, delta = 0): row and column of a clamped input
+    // zeroed, diagonal 1, its rows of H_ux zeroed; Cholesky, K columns
+    T H[NU17 * NU17], hx8[NU17];
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) {
+#pragma unroll
+      for (int j = 0; j <= i; ++j) H[i * NU17 + j] = csel(mf[i] | mf[j], T(i == j ? 1 : 0), L.HU[j][i]);
+      hx8[i] = L.HU[i][7];
+    }
+    T Lc[NU17 * NU17];
+    chol_n<T, NU17>(H, Lc);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) ok = ok && (Lc[i * NU17 + i] == Lc[i * NU17 + i]);
+    qp_ok = qp_ok && ok;
+    T Ks[NU17], K8[NU17], nb[NU17];
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) nb[i] = csel(mf[i], T(0), -Gs[NX17 + i]);
+    chol_n_solve<T, NU17>(Lc, nb, Ks);
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) nb[i] = csel(mf[i], T(0), -hx8[i]);
+    chol_n_solve<T, NU17>(Lc, nb, K8);
+    // (a clamped row is +0 whatever sign the solve leaves)
+#pragma unroll
+    for (int i = 0; i < NU17; ++i) {
+      Ks[i] = csel(mf[i], T(0), Ks[i]);
+      K8[i] = csel(mf[i], T(0), K8[i]);
+    }
+    {   // K_k row-major [6][17]: each lane its state's column, and (all the same value) state 8's
+      T* kr = kbase + (int64_t)k * kst;
+#pragma unroll
+      for (int i = 0; i < NU17; ++i) {
+        kr[i * NX17 + s] = bad ? qnan : Ks[i];
+        kr[i * NX17 + OM] = bad ? qnan : K8[i];
+      }
+    }
+    // ---- P_new[:, s] = G_xx[:, s] + Hxu K[:, s] (the unmasked H_xu: K's clamped rows are 0)
+    T Pn[NX17];
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) Pn[i] = Gs[i];
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) {
+      diag16_sown(Pn, Gs[NX17 + n], Ks[n]);
+      Pn[OM] += hx8[n] * Ks[n];
+    }
+    T P88n = G88;
+#pragma unroll
+    for (int n = 0; n < NU17; ++n) P88n += hx8[n] * K8[n];
+    // symmetric by construction: entry (i, s) from the lane max(own, owner of i)
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) L.X[t][xpos(i)] = Pn[i];
+    wave_lds_sync();
+#pragma unroll
+    for (int i = 0; i < NX17; ++i) {
+      if (i == OM) {
+        Pc[i] = Pn[i];
+      } else {
+        const T o = L.X[tstate(i)][xpos(s)];
+        Pc[i] = csel(lane_mask(tstate(i) > t), o, Pn[i]);
+      }
+    }
+    P88 = P88n;
+    wave_lds_sync();
+  }
+
+  // ---- P_0: lane t its column s (row 8 included), the same entry again as row s of column 8,
+  // and (every lane the same value) the corner
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) pbase[i * NX17 + s] = bad ? qnan : Pc[i];
+  pbase[s * NX17 + OM] = bad ? qnan : Pc[OM];
+  pbase[OM * NX17 + OM] = bad ? qnan : P88;
+  if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : (qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL);
+}
+
 }  // namespace q17
 
 template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_t st) {
@@ -1798,5 +2019,14 @@ template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st
 }
 template hipError_t launch_vjp17<double>(const Vjp17Args<double>&, hipStream_t);
 template hipError_t launch_vjp17<float>(const Vjp17Args<float>&, hipStream_t);
+
+template <class T> hipError_t launch_gains17(const Gains17Args<T>& a, hipStream_t st) {
+  const Vjp17Args<T>& v = a.v;
+  hipLaunchKernelGGL((q17::vjp17_lin_kernel<T>), dim3((unsigned)((v.nb * v.N + GQ17 - 1) / GQ17)), dim3(64), 0, st, v);
+  hipLaunchKernelGGL((q17::gains17_kernel<T>), dim3((unsigned)((v.nb + q17::GR - 1) / q17::GR)), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+template hipError_t launch_gains17<double>(const Gains17Args<double>&, hipStream_t);
+template hipError_t launch_gains17<float>(const Gains17Args<float>&, hipStream_t);
 
 }  // namespace mpcb
