@@ -371,6 +371,81 @@ int mpcb_solve_gains(mpcb_handle* h, int64_t B,
                      void* K, void* P0, int32_t* status, void* hip_stream);
 
 /*
+ * mpcb_solve_iterate with the cost weights given per instance (12/4 model): the QP of
+ * mpcb_solve_iterate at (xbar, ubar) in which instance b's own Q, R and QN stand in place of the
+ * handle's (the stage cost stays s Q_b, s R_b with s = cfg.cost_scale; the terminal cost is QN_b).
+ * The model, wind, dt, cost_scale and the input box come from the handle.  For a cost predicted
+ * per sample by a network, or B candidate weightings in one batch.
+ *   Qw [B|1,nx,nx], Rw [B|1,nu,nu], QNw [B|1,nx,nx]   DEVICE arrays of the handle's dtype, row-major;
+ *        instance b's matrix starts at Qw + b * Qw_sb (elements; likewise Rw_sb, QNw_sb).  Stride 0
+ *        broadcasts one matrix, a stride may exceed the record length, a negative stride is
+ *        MPCB_E_INVALID.  A NULL pointer means the handle's own matrix.  The arrays need only
+ *        element alignment.  Each matrix must be symmetric (and Q, QN positive semidefinite, R
+ *        positive definite, as for mpcb_config): the library cannot check device data, and the
+ *        kernel reads row j as column j.
+ *   every other argument, the aliasing of X / U with xbar / ubar and the alignment rules are those
+ *   of mpcb_solve_iterate
+ * status[B]: MPCB_STATUS_OK; MPCB_STATUS_NAN for an instance with a non-finite entry anywhere in
+ * its inputs, the weights included (its u0, X and U are all NaN; the other instances keep their
+ * bits); MPCB_STATUS_QP_FAIL when a masked input Hessian H_uu is not positive definite;
+ * MPCB_STATUS_MAXITER as below.
+ * The input box (fp64 handles only) is solved by the primal-dual active set alone: full exchange of
+ * the infeasible set V with the Kim-Park safeguard (3 tries) and the least-index backup rule, at
+ * most min(cfg.max_as_iter, 48) passes, with no hand-over to the interior point, neither after the
+ * first pass nor at the cap.  An instance that has not converged by then gets MPCB_STATUS_MAXITER
+ * and the last pass's iterate.  A clamped component of U (and of u0) is the bound's value itself, so
+ * the rule of mpcb_solve_vjp recovers the final set from U.  mpcb_qp_stats is not updated by this
+ * call, and mpcb_last_kernels / mpcb_last_timing do not see it.
+ * One self-contained kernel (16 lanes per instance); the handle's tuned solve paths are not used,
+ * so with all three pointers NULL the result agrees with mpcb_solve_iterate to rounding, not bit
+ * for bit.  The workspace is allocated by the first call (MPCB_E_NOMEM) and is not counted by
+ * mpcb_workspace_bytes.
+ * MPCB_E_UNSUPPORTED: a 17/6 handle; an fp32 handle with box_u (the shared-weight fp32 box owes its
+ * accuracy to a refinement kernel that has no per-instance variant).  MPCB_E_INVALID: B > max_batch,
+ * a negative stride, a missing x0, xbar, ubar, xref, uref, u0 or status.
+ * Out of scope: the 17/6 model, rollout mode (mpcb_solve), mpcb_eval and mpcb_solve_gains at
+ * per-instance weights, fp32 with the input box, an interior-point fallback, the acados facade.
+ */
+int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B,
+                          const void* x0, int64_t x0_sb,
+                          const void* xbar, const void* ubar,
+                          const void* xref, int64_t xref_sb,
+                          const void* uref, int64_t uref_sb,
+                          const void* wind, int64_t wind_sb,
+                          const void* Qw, int64_t Qw_sb,
+                          const void* Rw, int64_t Rw_sb,
+                          const void* QNw, int64_t QNw_sb,
+                          void* u0, void* X, void* U, int32_t* status, void* hip_stream);
+
+/*
+ * mpcb_solve_vjp_w at per-instance weights: the product and the weight gradients of a
+ * mpcb_solve_iterate_pw step.  The arguments are those of mpcb_solve_vjp_w plus the six weight
+ * arguments of mpcb_solve_iterate_pw (NULL = the handle's matrix, strides as there, symmetric
+ * matrices).  The formulas, the symmetry convention, the NaN rule (the weights join it), the
+ * statuses and the active-set rule on U are those of mpcb_solve_vjp_w with instance b's matrices
+ * in place of the handle's.  gQ, gR and gQN are per instance as before; for weights that differ
+ * per instance they are the gradient itself and need no sum over B (for a broadcast matrix the
+ * caller sums).  Both dtypes, with and without the input box (the set is read from U, so an fp32
+ * handle with box_u is accepted here).  Without a weight output X, xref and uref are not read.
+ * mpcb_solve_vjp and mpcb_solve_vjp_w launch the kernels they always did.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle; MPCB_E_INVALID as for mpcb_solve_vjp_w, and for a negative
+ * weight stride.
+ */
+int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B,
+                      const void* xbar, const void* ubar,
+                      const void* X, const void* U,
+                      const void* xref, int64_t xref_sb,
+                      const void* uref, int64_t uref_sb,
+                      const void* wind, int64_t wind_sb,
+                      const void* Qw, int64_t Qw_sb,
+                      const void* Rw, int64_t Rw_sb,
+                      const void* QNw, int64_t QNw_sb,
+                      const void* gX, const void* gU,
+                      void* gx0, void* gxref, void* guref,
+                      void* gQ, void* gR, void* gQN,
+                      int32_t* status, void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */

@@ -22,7 +22,8 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
            'mpcb_sim_step', 'mpcb_gen_inputs', 'mpcb_histogram', 'mpcb_set_timing',
            'mpcb_last_timing', 'mpcb_set_params', 'mpcb_set_t_blast', 'mpcb_qp_stats', 'mpcb_poc_jacobians',
            'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp',
-           'mpcb_solve_vjp_w', 'mpcb_set_weights', 'mpcb_solve_gains')
+           'mpcb_solve_vjp_w', 'mpcb_set_weights', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
+           'mpcb_solve_vjp_pw')
 # ... and the entry points named after the 17/6 model's dimensions (the list above is held to the
 # header's names by a letters-only pattern; tests/test_gpu_vjp17.py checks these)
 EXPORTS_17 = ('mpcb_solve_vjp17',)
@@ -102,7 +103,8 @@ def load(path: str | None = None):
     lib.mpcb_plan_kernels.argtypes = [ctypes.POINTER(MpcbConfig), i64, i64, i32, i32, ctypes.c_char_p, i64]
     lib.mpcb_last_kernels.argtypes = [vp, ctypes.c_char_p, i64]
     for name in EXPORTS:
-        if name not in ('mpcb_last_error', 'mpcb_workspace_bytes', 'mpcb_solve_gains'):
+        if name not in ('mpcb_last_error', 'mpcb_workspace_bytes', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
+                        'mpcb_solve_vjp_pw'):
             getattr(lib, name).restype = i32
     got = int(lib.mpcb_abi_version())
     if got != ABI_VERSION:
@@ -122,6 +124,16 @@ def load(path: str | None = None):
         raise LibraryMissing(f'{p} has no mpcb_solve_gains: rebuild it (__graft_entry__.build())')
     lib.mpcb_solve_gains.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.mpcb_solve_gains.restype = i32
+    # (likewise: the per-instance-weight solve and its product)
+    for name in ('mpcb_solve_iterate_pw', 'mpcb_solve_vjp_pw'):
+        if not hasattr(lib, name):
+            raise LibraryMissing(f'{p} has no {name}: rebuild it (__graft_entry__.build())')
+    lib.mpcb_solve_iterate_pw.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                          vp, i64, vp, vp, vp, vp, vp]
+    lib.mpcb_solve_iterate_pw.restype = i32
+    lib.mpcb_solve_vjp_pw.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mpcb_solve_vjp_pw.restype = i32
     if path is None:
         _lib = lib
     return lib

@@ -126,6 +126,33 @@ class BatchedMPC:
     def _ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
+    def _pw_weights(self, B, Q, R, QN):
+        """Per-instance weight arguments as device matrices: a list of (tensor or None, stride) for
+        Q, R, QN.  A weight always carries a batch axis: 2-D [B|1, n] holds diagonals, 3-D
+        [B|1, n, n] matrices, which are passed as 0.5 (M + M^T).  Built on the device: no host read,
+        no synchronisation."""
+        torch = _torch()
+        if self.nx == 17:
+            raise ValueError('per-instance weights cover the 12/4 model only')
+        out = []
+        for name, w, n in (('Q', Q, self.nx), ('R', R, self.nu), ('QN', QN, self.nx)):
+            if w is None:
+                out.append((None, 0))
+                continue
+            if isinstance(w, np.ndarray) and not w.flags.writeable:
+                w = w.copy()   # torch.as_tensor warns on read-only arrays
+            t = torch.as_tensor(w, dtype=self.dtype, device=self._tdev)
+            if t.dim() == 2 and t.shape[1] == n:
+                t = torch.diag_embed(t)
+            elif t.dim() == 3 and tuple(t.shape[1:]) == (n, n):
+                t = 0.5 * (t + t.transpose(1, 2))
+            else:
+                raise ValueError(f'{name}: expected [B|1, {n}] (diagonals) or [B|1, {n}, {n}], got {tuple(t.shape)}')
+            if t.shape[0] != B and t.shape[0] != 1:
+                raise ValueError(f'{name}: batch {t.shape[0]} != {B}')
+            out.append((t.contiguous(), 0 if t.shape[0] == 1 else n * n))
+        return out
+
     # ------------------------------------------------------------------ API
     def solve(self, x0, x_ref, u_ref, wind=None, want_traj: bool = True, out=None):
         """One SQP_RTI step per instance, linearised at the RK4 rollout of u_ref from x0.
@@ -152,8 +179,15 @@ class BatchedMPC:
             self._ptr(self._status), self._stream()))
         return self._u0
 
-    def solve_iterate(self, x0, xbar, ubar, x_ref, u_ref, wind=None, out=None):
-        """acados SQP_RTI step from the persistent iterate (xbar [B,N+1,12], ubar [B,N,4])."""
+    def solve_iterate(self, x0, xbar, ubar, x_ref, u_ref, wind=None, out=None, Q=None, R=None, QN=None):
+        """acados SQP_RTI step from the persistent iterate (xbar [B,N+1,12], ubar [B,N,4]).
+
+        ``Q``, ``R``, ``QN``: cost weights per instance (mpcb_solve_iterate_pw; 12/4 model, fp64
+        with the input box).  Each carries a batch axis: 2-D ``[B|1, n]`` holds diagonals, 3-D
+        ``[B|1, n, n]`` symmetric matrices (passed as 0.5 (M + M^T)); None = the handle's matrix.
+        Any of them routes the call to that entry point, whose input box is the plain active set
+        (status 2 at its cap, no interior-point fallback; ``qp_stats`` is not updated); with all
+        three None the call is the shared-weight solve."""
         N = self.cfg.N
         x0, _ = self._dev(x0, (self.nx,), 'x0')
         B = x0.shape[0]
@@ -166,6 +200,17 @@ class BatchedMPC:
             self._outputs(B, True)
         else:
             self._u0, self._X, self._U, self._status = out
+        if Q is not None or R is not None or QN is not None:
+            if B > self.max_batch:
+                raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+            (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN)
+            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd)
+            _lib.check(self.lib.mpcb_solve_iterate_pw(
+                self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
+                self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb,
+                self._ptr(QNd), QN_sb, self._ptr(self._u0), self._ptr(self._X), self._ptr(self._U),
+                self._ptr(self._status), self._stream()))
+            return self._u0
         self._keep = (x0, xb, ub, xr, ur, wd)
         _lib.check(self.lib.mpcb_solve_iterate(
             self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
@@ -201,7 +246,7 @@ class BatchedMPC:
         return out
 
     def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None, X=None, x_ref=None,
-                          u_ref=None, weights=False, fixed=None, active_tol=None):
+                          u_ref=None, weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None):
         """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 17/6: below): with J the
         Jacobian of (X, U) with respect to (x0, x_ref, u_ref) at fixed xbar, ubar, wind, weights
         and active set, returns J^T (gX, gU) as a dict of device tensors ``gx0`` [B,12],
@@ -217,6 +262,11 @@ class BatchedMPC:
         the solve's output ``X`` [B,N+1,12] and ``U`` and its references ``x_ref`` [B|1,N+1,12],
         ``u_ref`` [B|1,N,4] (include/mpcb.h has the formula).
 
+        ``Q``, ``R``, ``QN`` (12/4): the per-instance weights the solve was given, by the shape
+        rule of ``solve_iterate`` (mpcb_solve_vjp_pw, both dtypes, with and without the box); the
+        product and, with ``weights=True``, gQ, gR, gQN are then taken at instance b's matrices,
+        and the weight gradients are each instance's own (no batch sum).
+
         On a 17/6 handle (mpcb_solve_vjp17; shapes with 17 and 6) the active set is an argument,
         because the interior point leaves U near its bounds and not on them: ``fixed`` is a
         bool / uint8 tensor [B,N,6], nonzero = clamped.  Without it, and with ``U`` on an input-box
@@ -226,7 +276,10 @@ class BatchedMPC:
         mu = 1e-6: omitting it there raises ``ValueError``.  Without ``fixed`` and ``U`` nothing is
         clamped.  The mask used is returned as ``fixed``.  A handle with the state box is refused;
         ``wind`` raises as in ``solve_iterate``."""
+        pw = Q is not None or R is not None or QN is not None
         if self.nx == 17:
+            if pw:
+                raise ValueError('per-instance weights cover the 12/4 model only')
             return self._solve_iterate_vjp17(xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed,
                                              active_tol)
         if fixed is not None or active_tol is not None:
@@ -248,6 +301,8 @@ class BatchedMPC:
                    gxref=torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev),
                    guref=torch.empty((B, N, self.nu), dtype=self.dtype, device=dev),
                    status=torch.empty((B,), dtype=torch.int32, device=dev))
+        Xd = xr = ur = None
+        xr_sb = ur_sb = 0
         if weights:
             if X is None or U is None or x_ref is None or u_ref is None:
                 raise ValueError('weights=True needs X, U, x_ref and u_ref of the solve')
@@ -257,6 +312,17 @@ class BatchedMPC:
             out.update(gQ=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev),
                        gR=torch.empty((B, self.nu, self.nu), dtype=self.dtype, device=dev),
                        gQN=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev))
+        if pw:
+            (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN)
+            self._keep_vjp = (xb, ub, gXd, gUd, Ud, wd, Xd, xr, ur, Qd, Rd, QNd)
+            _lib.check(self.lib.mpcb_solve_vjp_pw(
+                self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Xd), self._ptr(Ud), self._ptr(xr), xr_sb,
+                self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb,
+                self._ptr(QNd), QN_sb, self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']),
+                self._ptr(out['gxref']), self._ptr(out['guref']), self._ptr(out.get('gQ')),
+                self._ptr(out.get('gR')), self._ptr(out.get('gQN')), self._ptr(out['status']), self._stream()))
+            return out
+        if weights:
             self._keep_vjp = (xb, ub, gXd, gUd, Ud, wd, Xd, xr, ur)
             _lib.check(self.lib.mpcb_solve_vjp_w(
                 self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Xd), self._ptr(Ud), self._ptr(xr), xr_sb,
@@ -400,15 +466,17 @@ class BatchedMPC:
         return out
 
     def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
-                           active_tol=None):
+                           active_tol=None, per_instance_weights=False):
         """``solve_iterate`` as a differentiable torch operation: returns (u0, X, U) whose
         gradients flow to ``x0``, ``x_ref`` and ``u_ref`` and, when given, to the weight tensors
         ``Q``, ``R``, ``QN``, which the forward pass installs with ``set_weights`` (see
         ``mpc_blaster_amd.autograd``).  ``active_tol``: the 17/6 active-set tolerance of
-        ``solve_iterate_vjp``."""
+        ``solve_iterate_vjp``.  ``per_instance_weights=True`` (12/4): the weight tensors follow the
+        batch-axis rule of ``solve_iterate`` and go to the solve as arguments; the handle's weights
+        stay as they are and nothing synchronises."""
         from .autograd import solve_iterate_diff
         return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN,
-                                  active_tol=active_tol)
+                                  active_tol=active_tol, per_instance_weights=per_instance_weights)
 
     def set_weights(self, Q=None, R=None, QN=None):
         """New cost weights on this handle (mpcb_set_weights; acados ``cost_set(k, 'W', W)`` with

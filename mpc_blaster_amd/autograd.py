@@ -37,6 +37,16 @@ weights the forward pass solved with: it raises ``RuntimeError`` if ``set_weight
 forward pass with weight tensors) has changed the handle's weights in between.  Without weight
 arguments nothing of this applies and the layer is as before.
 
+Weights per instance (``per_instance_weights=True``, 12/4 model).  ``Q``, ``R``, ``QN`` then carry a
+batch axis: a 2-D tensor ``[B|1, n]`` holds diagonals, a 3-D tensor ``[B|1, n, n]`` symmetric
+matrices (``BatchedMPC.solve_iterate``'s rule).  They are arguments of the solve
+(``mpcb_solve_iterate_pw``) and of the backward pass (``mpcb_solve_vjp_pw``): the forward pass calls
+neither ``set_weights`` nor anything that synchronises, and the handle's weights stay as they were.
+Each weight tensor receives its gradient per instance in its own shape, the diagonal of gQ for a
+2-D tensor, summed over the batch only for a ``[1, ...]`` tensor; instances with forward status
+other than 0 get zeros.  With the input box the solve is the plain active set of
+``mpcb_solve_iterate_pw`` (fp64 only).  A 17/6 handle raises ``ValueError``.
+
 torch is imported on first use, as in ``api.py``.
 """
 from __future__ import annotations
@@ -53,9 +63,11 @@ def _function():
 
     class SolveIterate(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol):
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol, pw):
             N = mpc.cfg.N
             full = mpc.nx == 17
+            if pw and full:
+                raise ValueError('per_instance_weights covers the 12/4 model only')
             if full and mpc.cfg.lbx is not None:
                 raise ValueError('solve_iterate_diff does not cover the 17/6 state box: an active state row '
                                  'is a state equality of the adjoint problem (use a handle without lbx/ubx '
@@ -72,9 +84,15 @@ def _function():
                                  allow_broadcast=True)
             wts = (Q, R, QN)
             ctx.has_weights = any(w is not None for w in wts)
-            if ctx.has_weights:
-                mpc.set_weights(*wts)
-            u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd)   # fresh outputs
+            ctx.pw = bool(pw) and ctx.has_weights
+            wdet = [None if w is None else w.detach() for w in wts]
+            if ctx.pw:   # arguments of the solve: the handle keeps its weights
+                u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd, Q=wdet[0], R=wdet[1],
+                                       QN=wdet[2])
+            else:
+                if ctx.has_weights:
+                    mpc.set_weights(*wts)
+                u0 = mpc.solve_iterate(x0d, xb, ub, x_ref.detach(), u_ref.detach(), wind=wd)   # fresh outputs
             X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
             ctx.mpc = mpc
             ctx.full = full
@@ -88,6 +106,9 @@ def _function():
                 ctx.wmeta = [None if w is None else (tuple(w.shape), w.dtype) for w in wts]
                 ctx.wversion = mpc._weights_version
                 saved += [X, x_ref.detach(), u_ref.detach()]
+            if ctx.pw:
+                ctx.wpresent = [w is not None for w in wdet]
+                saved += [w for w in wdet if w is not None]
             ctx.save_for_backward(*saved)
             return u0, X, U
 
@@ -102,7 +123,19 @@ def _function():
             want_w = ctx.has_weights and any(need[7:10])
             gU = g_U.to(mpc.dtype).clone()
             gU[:, 0] += g_u0.to(mpc.dtype)
-            if want_w:
+            pwkw = {}
+            nsaved = len(ctx.saved_tensors)
+            if ctx.pw:
+                given = iter(ctx.saved_tensors[nsaved - sum(ctx.wpresent):])
+                pwkw = {k: next(given) for k, p in zip(('Q', 'R', 'QN'), ctx.wpresent) if p}
+                nsaved -= sum(ctx.wpresent)
+            if ctx.pw and want_w:
+                X, xr, ur = ctx.saved_tensors[nsaved - 3:nsaved]
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, X=X, x_ref=xr, u_ref=ur, weights=True,
+                                            wind=wd, **pwkw)
+            elif ctx.pw:
+                out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd, **pwkw)
+            elif want_w:
                 if mpc._weights_version != ctx.wversion:
                     raise RuntimeError('the weights of the MPC handle changed after the forward pass '
                                        '(set_weights or another forward with weight tensors): the '
@@ -125,23 +158,33 @@ def _function():
                     if ctx.wmeta[i] is None or not need[7 + i]:
                         continue
                     shape, dt = ctx.wmeta[i]
-                    g = torch.where(ok.reshape(-1, 1, 1), out[key], torch.zeros_like(out[key])).sum(dim=0)
+                    g = torch.where(ok.reshape(-1, 1, 1), out[key], torch.zeros_like(out[key]))
+                    if ctx.pw:   # per instance, in the tensor's shape; one row: the batch sum
+                        g = torch.diagonal(g, dim1=1, dim2=2) if len(shape) == 2 else g
+                        if shape[0] == 1 and g.shape[0] != 1:
+                            g = g.sum(dim=0, keepdim=True)
+                        wgrads[i] = g.reshape(shape).to(dt)
+                        continue
+                    g = g.sum(dim=0)
                     wgrads[i] = (torch.diagonal(g) if len(shape) == 1 else g).reshape(shape).to(dt)
             return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
-                    grads[2] if need[5] else None, None, *wgrads, None)
+                    grads[2] if need[5] else None, None, *wgrads, None, None)
 
     _FN = SolveIterate
     return _FN
 
 
 def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
-                       active_tol=None):
+                       active_tol=None, per_instance_weights=False):
     """(u0 [B,4], X [B,N+1,12], U [B,N,4]; 17 and 6 on the full model) of ``mpc.solve_iterate``,
     differentiable with respect to the torch tensors ``x0``, ``x_ref`` and ``u_ref`` and, when given, the weight tensors ``Q``, ``R``,
     ``QN`` (vectors or symmetric matrices; installed on the handle by the forward pass, a host
     synchronisation: module docstring).  ``active_tol``: the 17/6 active-set tolerance (module
-    docstring).  The per-instance status is ``mpc.get_status()``."""
+    docstring).  ``per_instance_weights=True``: the weight tensors carry a batch axis and are arguments
+    of the solve, not installed on the handle (module docstring).  The per-instance status is
+    ``mpc.get_status()``."""
     import torch
     x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
                         for t in (x0, x_ref, u_ref))
-    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol)
+    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol,
+                             bool(per_instance_weights))

@@ -12,7 +12,7 @@ from .api import BatchedMPC
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
                 xbar=None, ubar=None, diagnostics=False, resolve_every: int = 1, feedback: bool = False,
-                active_tol=None):
+                active_tol=None, weights=None):
     """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
 
     ``resolve_every = h > 1`` (h <= N) models a controller slower than the plant: the solve runs
@@ -25,11 +25,27 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     default (checked before the loop starts), optional elsewhere.  With the defaults every step
     solves, as before.
 
+    ``weights``: a dict with any of the keys ``Q``, ``R``, ``QN``, cost weights per instance by the
+    shape rule of ``BatchedMPC.solve_iterate`` (2-D [B|1, n] diagonals, 3-D [B|1, n, n] matrices),
+    passed to every solve: B candidate weightings run as one closed-loop batch (12/4 model).  Not
+    together with ``feedback=True``, whose gains use the handle's weights, nor with
+    ``diagnostics``, which evaluates the handle's cost.
+
     ``diagnostics=True`` evaluates the new iterate after each solve (``BatchedMPC.evaluate`` with
     that step's x0) and returns a fourth value: a dict of [B, nsim] tensors ``cost``, ``res_eq``,
     ``res_stat`` (without ``res_stat`` on a handle with a state box)."""
     import torch
     h = int(resolve_every)
+    wkw = {}
+    if weights is not None:
+        unknown = set(weights) - {'Q', 'R', 'QN'}
+        if unknown:
+            raise ValueError(f'weights: unknown keys {sorted(unknown)} (expected Q, R, QN)')
+        if feedback:
+            raise ValueError('feedback=True uses the gains of the handle\'s weights: not together with weights')
+        if diagnostics:
+            raise ValueError('diagnostics evaluates the handle\'s cost: not together with weights')
+        wkw = {k: v for k, v in weights.items() if v is not None}
     if h < 1 or h > mpc.cfg.N:
         raise ValueError(f'resolve_every = {resolve_every}: expected 1 <= resolve_every <= N = {mpc.cfg.N}')
     if h > 1 or feedback:
@@ -37,7 +53,7 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
             raise ValueError('diagnostics evaluates every step\'s solve: use resolve_every=1, feedback=False')
         if feedback and active_tol is None and mpc.nx == 17 and mpc.cfg.boxed and mpc.cfg.dtype != 'f64':
             raise ValueError('feedback=True on an f32 17/6 input-box handle needs active_tol (solve_iterate_gains)')
-        return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol)
+        return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw)
     if active_tol is not None:
         raise ValueError('active_tol belongs to feedback=True')
     dev = f'cuda:{mpc.device}'
@@ -59,7 +75,7 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     diag = {k: torch.empty((B, nsim), dtype=dt, device=dev)
             for k in ('cost', 'res_eq') + (('res_stat',) if stat else ())} if diagnostics else None
     for i in range(nsim):
-        mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st))
+        mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw)
         worst = torch.maximum(worst, st)
         Us[:, i] = u0
         if diagnostics:
@@ -73,7 +89,7 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     return Xs, Us, worst
 
 
-def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol):
+def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw):
     """closed_loop with a solve every h plant steps and, optionally, the feedback law between."""
     import numpy as np
     import torch
@@ -104,7 +120,7 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
         if j == 0:
             if feedback:
                 xb0, ub0 = xb.clone(), ub.clone()   # the solve overwrites the iterate in place
-            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st))
+            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw)
             worst = torch.maximum(worst, st)
             if feedback:
                 g = mpc.solve_iterate_gains(xb0, ub0, U=ub if box else None, wind=wind, want_P0=False,

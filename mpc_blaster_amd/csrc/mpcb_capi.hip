@@ -16,6 +16,7 @@
 #include "mpcb_kernels.h"
 #include "mpcb_vjp.h"
 #include "mpcb_gains.h"
+#include "mpcb_pw.h"
 
 using namespace mpcb;
 
@@ -107,6 +108,8 @@ struct mpcb_handle {
   int gains_grid = 0;            // ... its resident slots; the 17/6 model uses vjp17_scratch
   void* vjp17_scratch = nullptr; // mpcb_solve_vjp17's chunk workspace: allocated by its first call, not
                                  // counted in scratch_bytes
+  void* pw_scratch = nullptr;    // mpcb_solve_iterate_pw's slot workspace: allocated by its first call,
+  int pw_grid = 0;               // not counted in scratch_bytes; its resident slots
 };
 
 // A 17/6 call over B instances may only read parameter rows that exist (mpcb_set_params count).
@@ -508,6 +511,7 @@ extern "C" int mpcb_destroy(mpcb_handle* h) {
   if (h->vjp_scratch) (void)hipFree(h->vjp_scratch);
   if (h->vjp17_scratch) (void)hipFree(h->vjp17_scratch);
   if (h->gains_scratch) (void)hipFree(h->gains_scratch);
+  if (h->pw_scratch) (void)hipFree(h->pw_scratch);
   delete h;
   return MPCB_OK;
 }
@@ -934,7 +938,9 @@ template <class T>
 static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* X, const void* U,
                     const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
                     const void* wind, int64_t wind_sb, const void* gX, const void* gU, void* gx0,
-                    void* gxref, void* guref, void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
+                    void* gxref, void* guref, void* gQ, void* gR, void* gQN, int32_t* status, void* stream,
+                    bool pw = false, const void* Qw = nullptr, int64_t Qw_sb = 0, const void* Rw = nullptr,
+                    int64_t Rw_sb = 0, const void* QNw = nullptr, int64_t QNw_sb = 0) {
   const int64_t slot = vjp_slot_elems(h->cfg.N);
   if (!h->vjp_scratch) {
     // resident slots: at most 8 one-wave workgroups per CU fit (registers: <= 2 waves per SIMD)
@@ -971,6 +977,11 @@ static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* uba
   a.xref = (const T*)xref; a.xref_sb = xref_sb;
   a.uref = (const T*)uref; a.uref_sb = uref_sb;
   a.gQ = (T*)gQ; a.gR = (T*)gR; a.gQN = (T*)gQN;
+  if (pw) {   // per-instance weights; NULL = the handle's own matrix for every instance
+    a.Qw = Qw ? (const T*)Qw : a.W->Q;     a.Qw_sb = Qw ? Qw_sb : 0;
+    a.Rw = Rw ? (const T*)Rw : a.W->R;     a.Rw_sb = Rw ? Rw_sb : 0;
+    a.QNw = QNw ? (const T*)QNw : a.W->QN; a.QNw_sb = QNw ? QNw_sb : 0;
+  }
   a.status = status;
   a.scratch = (T*)h->vjp_scratch;
   a.slot_elems = slot;
@@ -1005,6 +1016,112 @@ extern "C" int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B, const void* xbar, con
                             gxref, guref, gQ, gR, gQN, status, stream);
   return vjp_impl<float>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
                          gxref, guref, gQ, gR, gQN, status, stream);
+}
+
+extern "C" int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* X,
+                                 const void* U, const void* xref, int64_t xref_sb, const void* uref,
+                                 int64_t uref_sb, const void* wind, int64_t wind_sb, const void* Qw,
+                                 int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw, int64_t QNw_sb,
+                                 const void* gX, const void* gU, void* gx0, void* gxref, void* guref, void* gQ,
+                                 void* gR, void* gQN, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance weights cover the 12/4 model only");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  const bool wg = gQ || gR || gQN;
+  if (h->cfg.box_u && !U) return fail(MPCB_E_INVALID, "U is required on an input-box handle (the active set)");
+  if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
+  if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
+  if (int rc = check_strides(xref_sb, uref_sb, wind_sb)) return rc;
+  if (int rc = check_strides(Qw_sb, Rw_sb, QNw_sb)) return rc;
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (wg && (!X || !U || !xref || !uref))
+    return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->cfg.dtype == MPCB_F64)
+    return vjp_impl<double>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
+                            gxref, guref, gQ, gR, gQN, status, stream, true, Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb);
+  return vjp_impl<float>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
+                         gxref, guref, gQ, gR, gQN, status, stream, true, Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb);
+}
+
+template <class T>
+static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar, const void* ubar,
+                   const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb, const void* wind,
+                   int64_t wind_sb, const void* Qw, int64_t Qw_sb, const void* Rw, int64_t Rw_sb,
+                   const void* QNw, int64_t QNw_sb, void* u0, void* X, void* U, int32_t* status, void* stream) {
+  const int64_t slot = pw_slot_elems(h->cfg.N, h->cfg.box_u);
+  if (!h->pw_scratch) {
+    // resident slots: at most 6 one-wave workgroups per CU fit (LDS: the exchange rows and the
+    // weights of 4 instances, 24.6 KB in fp64)
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    int64_t grid = (int64_t)cus * 6;
+    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
+    // MPCB_PW_SLOTS: fewer slots, so that a small batch strides over them (tests)
+    if (const char* e = getenv("MPCB_PW_SLOTS"))
+      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
+    if (grid > waves) grid = waves;
+    if (grid < 1) grid = 1;
+    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
+    const hipError_t e = hipMalloc(&h->pw_scratch, bytes);
+    if (e != hipSuccess) {
+      h->pw_scratch = nullptr;
+      return fail(MPCB_E_NOMEM, "per-instance-weight workspace %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    h->pw_grid = (int)grid;
+  }
+  PwArgs<T> a;
+  a.B = B;
+  a.N = h->cfg.N;
+  a.box = h->cfg.box_u;
+  // the active set's cap: no hand-over to the interior point, neither early nor after the cap
+  a.max_as_iter = h->cfg.max_as_iter < AS_IPM_AFTER ? h->cfg.max_as_iter : AS_IPM_AFTER;
+  if (a.max_as_iter < 1) a.max_as_iter = 1;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.W = (const Weights<T>*)h->weights;
+  a.x0 = (const T*)x0; a.x0_sb = x0_sb;
+  a.xref = (const T*)xref; a.xref_sb = xref_sb;
+  a.uref = (const T*)uref; a.uref_sb = uref_sb;
+  a.wind = (const T*)wind; a.wind_sb = wind_sb;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
+  // NULL = the handle's own matrix for every instance
+  a.Qw = Qw ? (const T*)Qw : a.W->Q;     a.Qw_sb = Qw ? Qw_sb : 0;
+  a.Rw = Rw ? (const T*)Rw : a.W->R;     a.Rw_sb = Rw ? Rw_sb : 0;
+  a.QNw = QNw ? (const T*)QNw : a.W->QN; a.QNw_sb = QNw ? QNw_sb : 0;
+  a.u0 = (T*)u0; a.X = (T*)X; a.U = (T*)U;
+  a.status = status;
+  a.scratch = (T*)h->pw_scratch;
+  a.slot_elems = slot;
+  int64_t grid = (B + GROUPS - 1) / GROUPS;
+  if (grid > h->pw_grid) grid = h->pw_grid;
+  const hipError_t e = launch_pw<T>(a, (int)grid, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "per-instance-weight solve launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
+                                     const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
+                                     int64_t uref_sb, const void* wind, int64_t wind_sb, const void* Qw,
+                                     int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw,
+                                     int64_t QNw_sb, void* u0, void* X, void* U, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance weights cover the 12/4 model only");
+  if (h->cfg.box_u && h->cfg.dtype != MPCB_F64)
+    return fail(MPCB_E_UNSUPPORTED, "per-instance weights with the input box need an fp64 handle");
+  int rc = check_solve(h, B, x0, x0_sb, xref, xref_sb, uref, uref_sb, wind_sb, u0, X, U, status);
+  if (!rc) rc = check_strides(Qw_sb, Rw_sb, QNw_sb);
+  if (rc || B == 0) return rc;
+  if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->cfg.dtype == MPCB_F64)
+    return pw_impl<double>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb,
+                           Rw, Rw_sb, QNw, QNw_sb, u0, X, U, status, stream);
+  return pw_impl<float>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb, Rw,
+                        Rw_sb, QNw, QNw_sb, u0, X, U, status, stream);
 }
 
 // no weight output: the plain kernels, which read neither X nor the references

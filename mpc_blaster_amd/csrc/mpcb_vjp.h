@@ -1,5 +1,5 @@
 // mpcb_vjp.h — launch interface of the SQP_RTI step's vector-Jacobian product (mpcb_vjp.hip;
-// mpcb_solve_vjp and mpcb_solve_vjp_w in include/mpcb.h).  Internal to the library.
+// mpcb_solve_vjp, mpcb_solve_vjp_w and mpcb_solve_vjp_pw in include/mpcb.h).  Internal to the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +30,11 @@ struct VjpArgs {
   const T* xref; int64_t xref_sb;    // the solve's references and per-instance strides (0 = broadcast)
   const T* uref; int64_t uref_sb;
   T* gQ; T* gR; T* gQN;              // [B, nx, nx], [B, nu, nu], [B, nx, nx], each nullable
+  // per-instance weights (mpcb_solve_vjp_pw): Qw non-null selects the kernel variant that reads
+  // instance b's matrices at Qw + b * Qw_sb and so on (all three set then; stride 0 = one for all)
+  const T* Qw = nullptr; int64_t Qw_sb = 0;
+  const T* Rw = nullptr; int64_t Rw_sb = 0;
+  const T* QNw = nullptr; int64_t QNw_sb = 0;
 };
 
 // elements of one workspace slot: the captured linearisation scalars and the gains of N stages

@@ -44,7 +44,13 @@ constexpr int VJP_KR = 4;   // gain values per lane and stage: lane j < NX colum
 // row m of the R sum, per instance (the caller sums over the batch; no atomics).  X, U and the
 // references are read in pass 1 by the lane that owns the stage, for the check sum, and again in
 // pass 3.  The rows meet in LDS, where entry (r, c), c <= r, is formed once and stored to both places.
-template <class T, int BOX, int WG>
+//
+// PW: the weights are instance b's own (mpcb_solve_vjp_pw): Q, R and QN at a.Qw + b * a.Qw_sb and
+// so on instead of the handle's block (the box still comes from there).  Lane j keeps column j of
+// blkdiag(Q, R) in registers (the matrices are symmetric: also its row) and reads its column of QN
+// where the terminal stage needs it; these loads join the check sum.  The other instantiations do
+// not change.
+template <class T, int BOX, int WG, int PW = 0>
 __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
   __shared__ GroupLds<T> lds_all[GROUPS];
   const int lane = threadIdx.x;
@@ -72,6 +78,19 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
     }
     const T* xbp = a.xbar + b * (int64_t)(N + 1) * NX;
     const T* ubp = a.ubar + b * (int64_t)N * NU;
+    // (PW) the lane's column of blkdiag(Q, R) and where its column of QN starts
+    T wcol[NX];
+    const T* qnp = nullptr;
+    if constexpr (PW) {
+      const T* Qp = a.Qw + b * a.Qw_sb;
+      const T* Rp = a.Rw + b * a.Rw_sb;
+      qnp = a.QNw + b * a.QNw_sb + jx;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        wcol[i] = j < NX ? Qp[i * NX + jx] : (i < NU ? Rp[i * NU + ju] : T(0));
+        chk += wcol[i] * T(0);
+      }
+    }
     const T* gXp = a.gX ? a.gX + b * (int64_t)(N + 1) * NX : nullptr;
     const T* gUp = a.gU ? a.gU + b * (int64_t)N * NU : nullptr;
     // (WG) the solve's output and its references
@@ -139,8 +158,17 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
       chk += gN * T(0);
       pj = -gN;
       if (j < NX) {
+        if constexpr (PW) {
 #pragma unroll
-        for (int i = 0; i < NX; ++i) L.P[j * NX + i] = W.QN[i * NX + j];
+          for (int i = 0; i < NX; ++i) {
+            const T v = qnp[i * NX];
+            chk += v * T(0);
+            L.P[j * NX + i] = v;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) L.P[j * NX + i] = W.QN[i * NX + j];
+        }
       }
       __syncthreads();
     }
@@ -192,7 +220,15 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
         for (int l = 0; l < NX; ++l) acc += L.X[i * NX + l] * y[l];
         G[i] = acc;
       }
-      if (j < NX) {
+      if constexpr (PW) {
+        if (j < NX) {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) G[i] += s * wcol[i];
+        } else {
+#pragma unroll
+          for (int n = 0; n < NU; ++n) G[NX + n] += s * wcol[n];
+        }
+      } else if (j < NX) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) G[i] += s * W.Q[i * NX + jx];
       } else {
@@ -318,7 +354,15 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
         }
         // component j of s blkdiag(Q, R) (dx_k, du_k)
         T acc = T(0);
-        if (j < NX) {
+        if constexpr (PW) {
+          if (j < NX) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) acc += wcol[i] * dxk[i];
+          } else {
+#pragma unroll
+            for (int n = 0; n < NU; ++n) acc += wcol[n] * duk[n];
+          }
+        } else if (j < NX) {
 #pragma unroll
           for (int i = 0; i < NX; ++i) acc += W.Q[jx * NX + i] * dxk[i];
         } else {
@@ -361,8 +405,13 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
       }
       if (valid && gxrefp && j < NX) {
         T acc = T(0);
+        if constexpr (PW) {
 #pragma unroll
-        for (int i = 0; i < NX; ++i) acc += W.QN[jx * NX + i] * dxk[i];
+          for (int i = 0; i < NX; ++i) acc += qnp[i * NX] * dxk[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < NX; ++i) acc += W.QN[jx * NX + i] * dxk[i];
+        }
         gxrefp[(b * (N + 1) + N) * NX + j] = bad ? qnan : acc;
       }
       if constexpr (WG) {
@@ -414,6 +463,17 @@ int64_t vjp_slot_elems(int N) { return (int64_t)N * (GROUPS * LIN_STAGE + 64 * V
 
 template <class T> hipError_t launch_vjp(const VjpArgs<T>& a, int grid, hipStream_t st) {
   const bool wg = a.gQ || a.gR || a.gQN;   // no weight gradient asked for: the plain kernels
+  if (a.Qw) {   // per-instance weights (mpcb_solve_vjp_pw): all three pointers are set
+    if (a.box && wg)
+      hipLaunchKernelGGL((vjp_kernel<T, 1, 1, 1>), dim3(grid), dim3(64), 0, st, a);
+    else if (wg)
+      hipLaunchKernelGGL((vjp_kernel<T, 0, 1, 1>), dim3(grid), dim3(64), 0, st, a);
+    else if (a.box)
+      hipLaunchKernelGGL((vjp_kernel<T, 1, 0, 1>), dim3(grid), dim3(64), 0, st, a);
+    else
+      hipLaunchKernelGGL((vjp_kernel<T, 0, 0, 1>), dim3(grid), dim3(64), 0, st, a);
+    return hipGetLastError();
+  }
   if (a.box && wg)
     hipLaunchKernelGGL((vjp_kernel<T, 1, 1>), dim3(grid), dim3(64), 0, st, a);
   else if (wg)
