@@ -62,6 +62,31 @@ enum { MPCB_STATUS_OK = 0, MPCB_STATUS_NAN = 1, MPCB_STATUS_MAXITER = 2, MPCB_ST
 #define MPCB_MAX_NU 6
 
 /*
+ * A vehicle per instance (12/4 model): the model record.  One instance's vehicle is MPCB_MODEL_REC
+ * elements of the handle's dtype in a DEVICE array:
+ *   [0] mass  [1] lx  [2] ly  [3] c  [4] t_blast  [5..13] J, row-major 3x3
+ * Gravity, dt and the boxes stay with the handle.  The entry points that take a record
+ * (mpcb_sim_step_pm, mpcb_solve_iterate_pm, mpcb_solve_gains_pm) take it as `model, model_sb`:
+ *   instance b's record starts at model + b * model_sb, in elements;
+ *   model_sb == 0 broadcasts one record; model_sb >= MPCB_MODEL_REC is allowed and the pad elements
+ *   are never read; 0 < model_sb < MPCB_MODEL_REC or a negative stride is MPCB_E_INVALID;
+ *   the array needs element alignment only;
+ *   model == NULL means the handle's own model, and the call then launches the kernels of its
+ *   counterpart without `_pm` and returns its bits.
+ * The device derives 1 / mass and the inverse of J: the inverse by the adjugate formula in fp64
+ * from the record's values, rounded to the handle's dtype, so a record equal to the handle's config
+ * gives the handle's own model up to the rounding of the division order.  The library cannot
+ * validate device data: mass > 0 and a symmetric positive definite (so invertible) J are the
+ * caller's contract.  Every record entry joins the NaN rule of the call it is given to.
+ * Out of scope, each refused or absent: the 17/6 model (its per-instance data are mpcb_set_params);
+ * rollout mode (mpcb_solve); the tuned shared-weight solve paths (mpcb_solve_iterate and the bench
+ * configs c1-c5 keep one vehicle per handle); mpcb_eval, mpcb_linearize, the mpcb_solve_vjp family
+ * and the torch layer at per-instance models; gradients with respect to the model; fp32 with the
+ * input box; per-instance gravity, dt or boxes.
+ */
+#define MPCB_MODEL_REC 14
+
+/*
  * Problem definition: replaces the ``blasterModel(mass, J, l_x, l_y, N, Tf, c, Q, R, Q_t,
  * blastThruster, statesBound, controlBound)`` constructor + ``generateController()``
  * (src/scripts/blastermodel.py:16, :214-292) that build the acados OCP.
@@ -418,6 +443,59 @@ int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B,
                           void* u0, void* X, void* U, int32_t* status, void* hip_stream);
 
 /*
+ * mpcb_solve_iterate_pw with a vehicle per instance (12/4 model): the QP of mpcb_solve_iterate_pw at
+ * (xbar, ubar) with instance b's own mass, arms, yaw coefficient, T_blast and inertia (the model
+ * record, MPCB_MODEL_REC above) in the RK4 rollout, the gaps and the sensitivities.  For a
+ * controller whose belief about the vehicle differs per instance: an estimated payload, a tank that
+ * empties in flight, B candidate vehicles in one batch.
+ *   model, model_sb   the records, by the rules at MPCB_MODEL_REC; NULL = the handle's model, the
+ *                     kernels of mpcb_solve_iterate_pw and its bits
+ *   Qw, Rw, QNw and every other argument: as for mpcb_solve_iterate_pw, NULL and stride rules
+ *   included; per-instance weights and a per-instance model combine freely
+ * The statuses, the NaN rule (the record's 14 entries join it: an instance with a non-finite entry
+ * gets MPCB_STATUS_NAN and NaN in u0, X and U, the others keep their bits), the input box (fp64
+ * only, the plain active set with its cap, no interior-point hand-over), the aliasing of X / U with
+ * xbar / ubar, the alignment rules and the first-call workspace (shared with
+ * mpcb_solve_iterate_pw) are those of mpcb_solve_iterate_pw.  The same kernel with the instance's
+ * vehicle held in LDS (fp64, 24 values) or in its lanes' registers (fp32).
+ * MPCB_E_UNSUPPORTED: a 17/6 handle; an fp32 handle with box_u.  MPCB_E_INVALID: as for
+ * mpcb_solve_iterate_pw, and a model stride that is negative or between 1 and MPCB_MODEL_REC - 1.
+ */
+int mpcb_solve_iterate_pm(mpcb_handle* h, int64_t B,
+                          const void* x0, int64_t x0_sb,
+                          const void* xbar, const void* ubar,
+                          const void* xref, int64_t xref_sb,
+                          const void* uref, int64_t uref_sb,
+                          const void* wind, int64_t wind_sb,
+                          const void* Qw, int64_t Qw_sb,
+                          const void* Rw, int64_t Rw_sb,
+                          const void* QNw, int64_t QNw_sb,
+                          const void* model, int64_t model_sb,
+                          void* u0, void* X, void* U, int32_t* status, void* hip_stream);
+
+/*
+ * mpcb_solve_gains with a vehicle per instance (12/4 model): K_k and P_0 of the LQ problem that
+ * mpcb_solve_iterate_pm solves with the handle's weights, i.e. the recursion documented at
+ * mpcb_solve_gains with [A_k | B_k] the RK4 sensitivities of instance b's vehicle.
+ *   model, model_sb   the records, by the rules at MPCB_MODEL_REC; NULL = the handle's model, the
+ *                     kernels of mpcb_solve_gains and its bits
+ *   every other argument: as for mpcb_solve_gains on a 12/4 handle
+ * The weights are the handle's: there is no per-instance-weight variant of the gains.  The mask
+ * rules (fixed, or U on an input-box handle), the N <= 64 limit for fixed, the statuses (a
+ * non-finite record entry: MPCB_STATUS_NAN and NaN outputs for that instance alone), the bitwise
+ * symmetric P0, the exactly-zero rows of clamped components and the first-call workspace (shared
+ * with mpcb_solve_gains) are as documented there.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle.  MPCB_E_INVALID: as for mpcb_solve_gains, and a model stride
+ * that is negative or between 1 and MPCB_MODEL_REC - 1.
+ */
+int mpcb_solve_gains_pm(mpcb_handle* h, int64_t B,
+                        const void* xbar, const void* ubar,
+                        const void* U, const uint8_t* fixed,
+                        const void* wind, int64_t wind_sb,
+                        const void* model, int64_t model_sb,
+                        void* K, void* P0, int32_t* status, void* hip_stream);
+
+/*
  * mpcb_solve_vjp_w at per-instance weights: the product and the weight gradients of a
  * mpcb_solve_iterate_pw step.  The arguments are those of mpcb_solve_vjp_w plus the six weight
  * arguments of mpcb_solve_iterate_pw (NULL = the handle's matrix, strides as there, symmetric
@@ -451,6 +529,21 @@ int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B,
  */
 int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
                   int64_t wind_sb, double T, void* x_out, void* hip_stream);
+
+/*
+ * mpcb_sim_step with a vehicle per instance (12/4 model): x_out[b] = Phi_b(x[b], u[b]), one RK4
+ * step of instance b's own vehicle (the model record, MPCB_MODEL_REC above).  The plant of a
+ * vehicle-parameter Monte Carlo: the truth each instance flies, whatever the controller believes.
+ *   model, model_sb   the records, by the rules at MPCB_MODEL_REC; NULL = mpcb_sim_step itself
+ *   every other argument: as for mpcb_sim_step
+ * There is no status: an instance with a non-finite record entry gets NaN in its whole x_out row,
+ * the other instances are unaffected.  A kernel of its own; mpcb_sim_step launches what it always did.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle (its per-instance data are mpcb_set_params).  MPCB_E_INVALID:
+ * as for mpcb_sim_step, and a model stride that is negative or between 1 and MPCB_MODEL_REC - 1.
+ */
+int mpcb_sim_step_pm(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
+                     int64_t wind_sb, const void* model, int64_t model_sb, double T, void* x_out,
+                     void* hip_stream);
 
 /*
  * Synthetic inputs (SURVEY §8 d): Philox4x32-10 keyed by (seed, id_offset + i).

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, LIB_NAME)
 ABI_VERSION = 5
 MPCB_F64, MPCB_F32 = 0, 1
 MPCB_MAX_NX, MPCB_MAX_NU = 17, 6
+MODEL_REC = 14   # MPCB_MODEL_REC: elements of one instance's vehicle record
 STATUS_OK, STATUS_NAN, STATUS_MAXITER, STATUS_MINSTEP, STATUS_QP_FAIL = 0, 1, 2, 3, 4
 
 EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
@@ -23,7 +24,10 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
            'mpcb_last_timing', 'mpcb_set_params', 'mpcb_set_t_blast', 'mpcb_qp_stats', 'mpcb_poc_jacobians',
            'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp',
            'mpcb_solve_vjp_w', 'mpcb_set_weights', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
-           'mpcb_solve_vjp_pw')
+           'mpcb_solve_vjp_pw', 'mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm')
+# the per-instance-model entry points among them (typed after the version check, like the others
+# that joined ABI version 5 without a new number)
+EXPORTS_PM = ('mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm')
 # ... and the entry points named after the 17/6 model's dimensions (the list above is held to the
 # header's names by a letters-only pattern; tests/test_gpu_vjp17.py checks these)
 EXPORTS_17 = ('mpcb_solve_vjp17',)
@@ -104,7 +108,7 @@ def load(path: str | None = None):
     lib.mpcb_last_kernels.argtypes = [vp, ctypes.c_char_p, i64]
     for name in EXPORTS:
         if name not in ('mpcb_last_error', 'mpcb_workspace_bytes', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
-                        'mpcb_solve_vjp_pw'):
+                        'mpcb_solve_vjp_pw') + EXPORTS_PM:
             getattr(lib, name).restype = i32
     got = int(lib.mpcb_abi_version())
     if got != ABI_VERSION:
@@ -134,6 +138,15 @@ def load(path: str | None = None):
     lib.mpcb_solve_vjp_pw.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mpcb_solve_vjp_pw.restype = i32
+    # (likewise: the per-instance-model plant step, solve and gains)
+    for name in EXPORTS_PM:
+        if not hasattr(lib, name):
+            raise LibraryMissing(f'{p} has no {name}: rebuild it (__graft_entry__.build())')
+        getattr(lib, name).restype = i32
+    lib.mpcb_sim_step_pm.argtypes = [vp, i64, vp, vp, vp, i64, vp, i64, dbl, vp, vp]
+    lib.mpcb_solve_iterate_pm.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                          vp, i64, vp, i64, vp, vp, vp, vp, vp]
+    lib.mpcb_solve_gains_pm.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib

@@ -153,6 +153,64 @@ class BatchedMPC:
             out.append((t.contiguous(), 0 if t.shape[0] == 1 else n * n))
         return out
 
+    def _model_arg(self, model, B):
+        """A ``model=`` argument as (device tensor, stride): vehicle records [B|1, 14] or [14]
+        (mpcb.h MPCB_MODEL_REC); wider rows are padding that the library never reads."""
+        torch = _torch()
+        if self.nx == 17:
+            raise ValueError('per-instance models cover the 12/4 model only (17/6: set_params)')
+        if isinstance(model, np.ndarray) and not model.flags.writeable:
+            model = model.copy()   # torch.as_tensor warns on read-only arrays
+        t = torch.as_tensor(model, dtype=self.dtype, device=self._tdev)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2 or t.shape[1] < _lib.MODEL_REC:
+            raise ValueError(f'model: expected [B|1, {_lib.MODEL_REC}] (or wider, padded rows), got {tuple(t.shape)}')
+        if t.shape[0] != B and t.shape[0] != 1:
+            raise ValueError(f'model: batch {t.shape[0]} != {B}')
+        t = t.contiguous()
+        return t, 0 if t.shape[0] == 1 else t.shape[1]
+
+    def pack_model(self, B=None, mass=None, J=None, lx=None, ly=None, c=None, t_blast=None):
+        """Vehicle records for ``sim_step`` / ``solve_iterate`` / ``solve_iterate_gains`` /
+        ``closed_loop`` (12/4 model; mpcb.h MPCB_MODEL_REC): a [B|1, 14] device tensor of the
+        handle's dtype, row = [mass, lx, ly, c, t_blast, J row-major].  Each scalar field is a
+        number, [B] or [1]; ``J`` is [3,3] (one matrix), [B,3,3] or [B,3] (diagonals; a [3,3]
+        argument is always one matrix).  An omitted field takes the handle's config value (the
+        current T_blast of ``set_t_blast``).  ``B`` None: the largest batch among the fields.
+        Built on the device: no host read-back, no synchronisation.  mass > 0 and a symmetric
+        positive definite J are the caller's contract."""
+        torch = _torch()
+        if self.nx == 17:
+            raise ValueError('per-instance models cover the 12/4 model only (17/6: set_params)')
+        cols = []
+        for name, v in (('mass', mass), ('lx', lx), ('ly', ly), ('c', c), ('t_blast', t_blast)):
+            if isinstance(v, np.ndarray) and not v.flags.writeable:
+                v = v.copy()   # torch.as_tensor warns on read-only arrays
+            t = torch.as_tensor(getattr(self.cfg, name) if v is None else v, dtype=self.dtype, device=self._tdev)
+            if t.dim() > 1:
+                raise ValueError(f'{name}: expected a scalar, [B] or [1], got {tuple(t.shape)}')
+            cols.append(t.reshape(-1, 1))
+        if J is None:
+            J = np.asarray(self.cfg.J, dtype=np.float64).reshape(3, 3).copy()
+        elif isinstance(J, np.ndarray) and not J.flags.writeable:
+            J = J.copy()
+        Jt = torch.as_tensor(J, dtype=self.dtype, device=self._tdev)
+        if tuple(Jt.shape) == (3, 3):
+            Jt = Jt.reshape(1, 9)
+        elif Jt.dim() == 3 and tuple(Jt.shape[1:]) == (3, 3):
+            Jt = Jt.reshape(-1, 9)
+        elif Jt.dim() == 2 and Jt.shape[1] == 3:
+            Jt = torch.diag_embed(Jt).reshape(-1, 9)
+        else:
+            raise ValueError(f'J: expected [3, 3], [B, 3, 3] or [B, 3] (diagonals), got {tuple(Jt.shape)}')
+        cols.append(Jt)
+        rows = max(t.shape[0] for t in cols) if B is None else int(B)
+        for name, t in zip(('mass', 'lx', 'ly', 'c', 't_blast', 'J'), cols):
+            if t.shape[0] != rows and t.shape[0] != 1:
+                raise ValueError(f'{name}: batch {t.shape[0]} != {rows}')
+        return torch.cat([t.expand(rows, t.shape[1]) for t in cols], dim=1).contiguous()
+
     # ------------------------------------------------------------------ API
     def solve(self, x0, x_ref, u_ref, wind=None, want_traj: bool = True, out=None):
         """One SQP_RTI step per instance, linearised at the RK4 rollout of u_ref from x0.
@@ -179,7 +237,8 @@ class BatchedMPC:
             self._ptr(self._status), self._stream()))
         return self._u0
 
-    def solve_iterate(self, x0, xbar, ubar, x_ref, u_ref, wind=None, out=None, Q=None, R=None, QN=None):
+    def solve_iterate(self, x0, xbar, ubar, x_ref, u_ref, wind=None, out=None, Q=None, R=None, QN=None,
+                      model=None):
         """acados SQP_RTI step from the persistent iterate (xbar [B,N+1,12], ubar [B,N,4]).
 
         ``Q``, ``R``, ``QN``: cost weights per instance (mpcb_solve_iterate_pw; 12/4 model, fp64
@@ -187,7 +246,12 @@ class BatchedMPC:
         ``[B|1, n, n]`` symmetric matrices (passed as 0.5 (M + M^T)); None = the handle's matrix.
         Any of them routes the call to that entry point, whose input box is the plain active set
         (status 2 at its cap, no interior-point fallback; ``qp_stats`` is not updated); with all
-        three None the call is the shared-weight solve."""
+        three None the call is the shared-weight solve.
+
+        ``model``: a vehicle per instance (mpcb_solve_iterate_pm; 12/4 model): records [B|1, 14]
+        as ``pack_model`` builds them (or wider, padded rows), an array or a tensor.  It combines
+        with ``Q``, ``R``, ``QN`` and has that entry point's input box and refusals; with
+        ``model=None`` the call takes the path it takes without the keyword."""
         N = self.cfg.N
         x0, _ = self._dev(x0, (self.nx,), 'x0')
         B = x0.shape[0]
@@ -200,6 +264,18 @@ class BatchedMPC:
             self._outputs(B, True)
         else:
             self._u0, self._X, self._U, self._status = out
+        if model is not None:
+            if B > self.max_batch:
+                raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+            md, m_sb = self._model_arg(model, B)
+            (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN)
+            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd, md)
+            _lib.check(self.lib.mpcb_solve_iterate_pm(
+                self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
+                self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb,
+                self._ptr(QNd), QN_sb, self._ptr(md), m_sb, self._ptr(self._u0), self._ptr(self._X),
+                self._ptr(self._U), self._ptr(self._status), self._stream()))
+            return self._u0
         if Q is not None or R is not None or QN is not None:
             if B > self.max_batch:
                 raise ValueError(f'batch {B} > max_batch {self.max_batch}')
@@ -410,7 +486,7 @@ class BatchedMPC:
         return out
 
     def solve_iterate_gains(self, xbar, ubar, U=None, fixed=None, active_tol=None, wind=None,
-                            want_K=True, want_P0=True):
+                            want_K=True, want_P0=True, model=None):
         """Feedback gains and cost-to-go Hessian of the ``solve_iterate`` step at (xbar, ubar)
         (mpcb_solve_gains; include/mpcb.h has the recursion): a dict of device tensors ``K``
         [B,N,nu,nx] (``U'_k - U_k = K_k (X'_k - X_k)`` between two solves that differ in x0 on one
@@ -427,7 +503,10 @@ class BatchedMPC:
         misses an instance the active set handed to the interior point: a tolerance finds it.  On
         17/6 ``U`` alone uses the default tolerance of ``solve_iterate_vjp`` (1e-6 on f64,
         required on f32).  Without ``fixed`` and ``U`` nothing is clamped.  A mask on a 12/4 handle
-        needs N <= 64 (``MpcbError``, MPCB_E_UNSUPPORTED); 17/6 has no such limit."""
+        needs N <= 64 (``MpcbError``, MPCB_E_UNSUPPORTED); 17/6 has no such limit.
+
+        ``model``: a vehicle per instance (mpcb_solve_gains_pm; 12/4 model), records [B|1, 14] as
+        for ``solve_iterate``: the gains of that solve with the handle's weights."""
         torch = _torch()
         if not want_K and not want_P0:
             raise ValueError('solve_iterate_gains: want_K and want_P0 are both False')
@@ -458,6 +537,14 @@ class BatchedMPC:
         out = dict(K=torch.empty((B, N, self.nu, self.nx), dtype=self.dtype, device=dev) if want_K else None,
                    P0=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev) if want_P0 else None,
                    status=torch.empty((B,), dtype=torch.int32, device=dev), fixed=fx)
+        if model is not None:
+            md, m_sb = self._model_arg(model, B)
+            self._keep_gains = (xb, ub, Ud, fx, wd, md)
+            _lib.check(self.lib.mpcb_solve_gains_pm(
+                self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Ud if fx is None else None), self._ptr(fx),
+                self._ptr(wd), wd_sb, self._ptr(md), m_sb, self._ptr(out['K']), self._ptr(out['P0']),
+                self._ptr(out['status']), self._stream()))
+            return out
         self._keep_gains = (xb, ub, Ud, fx, wd)
         _lib.check(self.lib.mpcb_solve_gains(
             self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(Ud if fx is None else None), self._ptr(fx),
@@ -595,14 +682,23 @@ class BatchedMPC:
         self._keep = (xb, ub, wd)
         return A, Bm, xn
 
-    def sim_step(self, x, u, T=None, wind=None):
-        """Plant integrator: one RK4 step of length T (default dt) — AcadosSimSolver.solve()."""
+    def sim_step(self, x, u, T=None, wind=None, model=None):
+        """Plant integrator: one RK4 step of length T (default dt) — AcadosSimSolver.solve().
+        ``model``: a vehicle per instance (mpcb_sim_step_pm; 12/4 model), records [B|1, 14] as
+        ``pack_model`` builds them; an instance with a non-finite record entry gets a NaN row."""
         torch = _torch()
         xs, _ = self._dev(x, (self.nx,), 'x')
         B = xs.shape[0]
         us, _ = self._dev(u, (self.nu,), 'u', B)
         wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
         xo = torch.empty_like(xs)
+        if model is not None:
+            md, m_sb = self._model_arg(model, B)
+            _lib.check(self.lib.mpcb_sim_step_pm(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(wd), wd_sb,
+                                                 self._ptr(md), m_sb, float(self.cfg.dt if T is None else T),
+                                                 self._ptr(xo), self._stream()))
+            self._keep = (xs, us, wd, md)
+            return xo
         _lib.check(self.lib.mpcb_sim_step(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(wd),
                                           wd_sb, float(self.cfg.dt if T is None else T),
                                           self._ptr(xo), self._stream()))

@@ -12,7 +12,7 @@ from .api import BatchedMPC
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
                 xbar=None, ubar=None, diagnostics=False, resolve_every: int = 1, feedback: bool = False,
-                active_tol=None, weights=None):
+                active_tol=None, weights=None, model=None, plant_model=None):
     """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
 
     ``resolve_every = h > 1`` (h <= N) models a controller slower than the plant: the solve runs
@@ -31,6 +31,12 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     together with ``feedback=True``, whose gains use the handle's weights, nor with
     ``diagnostics``, which evaluates the handle's cost.
 
+    ``model`` and ``plant_model`` (12/4 model): vehicle records [B|1, 14] as
+    ``BatchedMPC.pack_model`` builds them, in two roles.  ``model`` is the controller's belief: it
+    goes to every solve and, with ``feedback=True``, to the gains.  ``plant_model`` is the truth:
+    it goes to every plant step.  Either may be given alone; the other side then uses the handle's
+    vehicle.  ``model`` not together with ``diagnostics``, which evaluates with the handle's model.
+
     ``diagnostics=True`` evaluates the new iterate after each solve (``BatchedMPC.evaluate`` with
     that step's x0) and returns a fourth value: a dict of [B, nsim] tensors ``cost``, ``res_eq``,
     ``res_stat`` (without ``res_stat`` on a handle with a state box)."""
@@ -46,6 +52,18 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
         if diagnostics:
             raise ValueError('diagnostics evaluates the handle\'s cost: not together with weights')
         wkw = {k: v for k, v in weights.items() if v is not None}
+    mkw, pkw = {}, {}
+    if model is not None or plant_model is not None:
+        if mpc.nx == 17:
+            raise ValueError('model / plant_model cover the 12/4 model only (17/6: set_params)')
+        if diagnostics and model is not None:
+            raise ValueError('diagnostics evaluates with the handle\'s model: not together with model')
+        # records on the device once, not at every step (and checked against the batch here)
+        B0 = x0.shape[0] if hasattr(x0, 'shape') else len(x0)
+        if model is not None:
+            mkw = dict(model=mpc._model_arg(model, B0)[0])
+        if plant_model is not None:
+            pkw = dict(model=mpc._model_arg(plant_model, B0)[0])
     if h < 1 or h > mpc.cfg.N:
         raise ValueError(f'resolve_every = {resolve_every}: expected 1 <= resolve_every <= N = {mpc.cfg.N}')
     if h > 1 or feedback:
@@ -53,7 +71,8 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
             raise ValueError('diagnostics evaluates every step\'s solve: use resolve_every=1, feedback=False')
         if feedback and active_tol is None and mpc.nx == 17 and mpc.cfg.boxed and mpc.cfg.dtype != 'f64':
             raise ValueError('feedback=True on an f32 17/6 input-box handle needs active_tol (solve_iterate_gains)')
-        return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw)
+        return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw,
+                          mkw, pkw)
     if active_tol is not None:
         raise ValueError('active_tol belongs to feedback=True')
     dev = f'cuda:{mpc.device}'
@@ -75,21 +94,21 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     diag = {k: torch.empty((B, nsim), dtype=dt, device=dev)
             for k in ('cost', 'res_eq') + (('res_stat',) if stat else ())} if diagnostics else None
     for i in range(nsim):
-        mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw)
+        mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
         worst = torch.maximum(worst, st)
         Us[:, i] = u0
         if diagnostics:
             ev = mpc.evaluate(xb, ub, x_ref, u_ref, x0=x, wind=wind, stat=stat)
             for k, v in diag.items():
                 v[:, i] = ev[k]
-        x = mpc.sim_step(x, u0, T=plant_T, wind=wind)
+        x = mpc.sim_step(x, u0, T=plant_T, wind=wind, **pkw)
         Xs[:, i + 1] = x
     if diagnostics:
         return Xs, Us, worst, diag
     return Xs, Us, worst
 
 
-def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw):
+def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw, mkw, pkw):
     """closed_loop with a solve every h plant steps and, optionally, the feedback law between."""
     import numpy as np
     import torch
@@ -120,11 +139,11 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
         if j == 0:
             if feedback:
                 xb0, ub0 = xb.clone(), ub.clone()   # the solve overwrites the iterate in place
-            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw)
+            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
             worst = torch.maximum(worst, st)
             if feedback:
                 g = mpc.solve_iterate_gains(xb0, ub0, U=ub if box else None, wind=wind, want_P0=False,
-                                            active_tol=active_tol if box else None)
+                                            active_tol=active_tol if box else None, **mkw)
                 worst = torch.maximum(worst, g['status'])
                 K = g['K']
         u = ub[:, j]
@@ -134,6 +153,6 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
             u = torch.minimum(torch.maximum(u, lb), hb)
         u = u.contiguous()
         Us[:, i] = u
-        x = mpc.sim_step(x, u, T=plant_T, wind=wind)
+        x = mpc.sim_step(x, u, T=plant_T, wind=wind, **pkw)
         Xs[:, i + 1] = x
     return Xs, Us, worst

@@ -1,6 +1,8 @@
 // mpcb_aux.hip — linearisation (debug/parity), plant step, synthetic inputs, u0 histogram.
 #include <hip/hip_runtime.h>
 
+#include <limits>
+
 #include "../../include/mpcb.h"
 #include "mpcb_kernels.h"
 
@@ -85,6 +87,43 @@ hipError_t launch_sim_step(int64_t B, T h, const Model<T>& M, const T* x, const 
   const int64_t grid = (B + 255) / 256;
   hipLaunchKernelGGL((sim_step_kernel<T>), dim3((unsigned)grid), dim3(256), 0, st, B, h, M, x, u,
                      wind, wind_sb, xo);
+  return hipGetLastError();
+}
+
+// The plant step with a vehicle per instance (mpcb_sim_step_pm): a sibling of sim_step_kernel, which
+// stays as it is.  The thread builds its instance's Model<T> from the record (model_from_rec); a
+// non-finite record entry turns the instance's x_out into NaN by the check sum of the NaN rule.
+template <class T>
+__global__ void __launch_bounds__(256) sim_step_pm_kernel(int64_t B, T h, T g,
+                                                          const T* __restrict__ model, int64_t model_sb,
+                                                          const T* __restrict__ x,
+                                                          const T* __restrict__ u,
+                                                          const T* __restrict__ wind, int64_t wind_sb,
+                                                          T* __restrict__ xo) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  Model<T> M;
+  T chk = T(0);
+  model_from_rec<T>(model + b * model_sb, g, M, chk);
+  T w[3] = {T(0), T(0), T(0)};
+  if (wind) { w[0] = wind[b * wind_sb]; w[1] = wind[b * wind_sb + 1]; w[2] = wind[b * wind_sb + 2]; }
+  T xv[NX], uv[NU], xn[NX], dd[1];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xv[i] = x[b * NX + i];
+#pragma unroll
+  for (int m = 0; m < NU; ++m) uv[m] = u[b * NU + m];
+  rk4<T, false>(xv, nullptr, uv, nullptr, h, M, w, xn, dd);
+  const bool bad = chk != chk;
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xo[b * NX + i] = bad ? std::numeric_limits<T>::quiet_NaN() : xn[i];
+}
+
+template <class T>
+hipError_t launch_sim_step_pm(int64_t B, T h, T g, const T* model, int64_t model_sb, const T* x, const T* u,
+                              const T* wind, int64_t wind_sb, T* xo, hipStream_t st) {
+  const int64_t grid = (B + 255) / 256;
+  hipLaunchKernelGGL((sim_step_pm_kernel<T>), dim3((unsigned)grid), dim3(256), 0, st, B, h, g, model,
+                     model_sb, x, u, wind, wind_sb, xo);
   return hipGetLastError();
 }
 
@@ -259,6 +298,8 @@ hipError_t launch_quat_ops(int64_t B, const double* q1, const double* q2, double
                                           const T*, int64_t, T*, T*, T*, hipStream_t);           \
   template hipError_t launch_sim_step<T>(int64_t, T, const Model<T>&, const T*, const T*,        \
                                          const T*, int64_t, T*, hipStream_t);                    \
+  template hipError_t launch_sim_step_pm<T>(int64_t, T, T, const T*, int64_t, const T*, const T*, \
+                                            const T*, int64_t, T*, hipStream_t);                 \
   template hipError_t launch_gen_inputs<T>(int64_t, int, T, uint64_t, uint64_t, int, T*, T*,     \
                                            int64_t, T*, int64_t, T*, hipStream_t);               \
   template hipError_t launch_histogram<T>(int64_t, int, const T*, double, double, int,           \

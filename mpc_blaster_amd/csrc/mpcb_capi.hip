@@ -1050,7 +1050,8 @@ template <class T>
 static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar, const void* ubar,
                    const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb, const void* wind,
                    int64_t wind_sb, const void* Qw, int64_t Qw_sb, const void* Rw, int64_t Rw_sb,
-                   const void* QNw, int64_t QNw_sb, void* u0, void* X, void* U, int32_t* status, void* stream) {
+                   const void* QNw, int64_t QNw_sb, const void* model, int64_t model_sb, void* u0, void* X,
+                   void* U, int32_t* status, void* stream) {
   const int64_t slot = pw_slot_elems(h->cfg.N, h->cfg.box_u);
   if (!h->pw_scratch) {
     // resident slots: at most 6 one-wave workgroups per CU fit (LDS: the exchange rows and the
@@ -1092,6 +1093,7 @@ static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, con
   a.Qw = Qw ? (const T*)Qw : a.W->Q;     a.Qw_sb = Qw ? Qw_sb : 0;
   a.Rw = Rw ? (const T*)Rw : a.W->R;     a.Rw_sb = Rw ? Rw_sb : 0;
   a.QNw = QNw ? (const T*)QNw : a.W->QN; a.QNw_sb = QNw ? QNw_sb : 0;
+  a.model = (const T*)model; a.model_sb = model ? model_sb : 0;
   a.u0 = (T*)u0; a.X = (T*)X; a.U = (T*)U;
   a.status = status;
   a.scratch = (T*)h->pw_scratch;
@@ -1103,25 +1105,49 @@ static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, con
   return MPCB_OK;
 }
 
-extern "C" int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
+// A vehicle record's stride (MPCB_MODEL_REC): 0 broadcasts one record, otherwise a whole record at
+// the least.
+static int check_model_stride(int64_t model_sb) {
+  if (model_sb < 0 || (model_sb > 0 && model_sb < MPCB_MODEL_REC))
+    return fail(MPCB_E_INVALID, "model stride %lld: 0 (broadcast) or >= %d", (long long)model_sb, MPCB_MODEL_REC);
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_iterate_pm(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
                                      const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
                                      int64_t uref_sb, const void* wind, int64_t wind_sb, const void* Qw,
                                      int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw,
-                                     int64_t QNw_sb, void* u0, void* X, void* U, int32_t* status, void* stream) {
+                                     int64_t QNw_sb, const void* model, int64_t model_sb, void* u0, void* X,
+                                     void* U, int32_t* status, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
-  if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance weights cover the 12/4 model only");
+  // (a caller of mpcb_solve_iterate_pw, which passes no model, reads the messages it always read)
+  if (h->full)
+    return fail(MPCB_E_UNSUPPORTED, model ? "per-instance models cover the 12/4 model only (17/6: mpcb_set_params)"
+                                          : "per-instance weights cover the 12/4 model only");
   if (h->cfg.box_u && h->cfg.dtype != MPCB_F64)
-    return fail(MPCB_E_UNSUPPORTED, "per-instance weights with the input box need an fp64 handle");
+    return fail(MPCB_E_UNSUPPORTED, model ? "per-instance models with the input box need an fp64 handle"
+                                          : "per-instance weights with the input box need an fp64 handle");
   int rc = check_solve(h, B, x0, x0_sb, xref, xref_sb, uref, uref_sb, wind_sb, u0, X, U, status);
   if (!rc) rc = check_strides(Qw_sb, Rw_sb, QNw_sb);
+  if (!rc) rc = check_model_stride(model_sb);
   if (rc || B == 0) return rc;
   if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
   HIP_TRY(hipSetDevice(h->device));
   if (h->cfg.dtype == MPCB_F64)
     return pw_impl<double>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb,
-                           Rw, Rw_sb, QNw, QNw_sb, u0, X, U, status, stream);
+                           Rw, Rw_sb, QNw, QNw_sb, model, model_sb, u0, X, U, status, stream);
   return pw_impl<float>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb, Rw,
-                        Rw_sb, QNw, QNw_sb, u0, X, U, status, stream);
+                        Rw_sb, QNw, QNw_sb, model, model_sb, u0, X, U, status, stream);
+}
+
+// the handle's model: the kernels this call always launched
+extern "C" int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
+                                     const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
+                                     int64_t uref_sb, const void* wind, int64_t wind_sb, const void* Qw,
+                                     int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw,
+                                     int64_t QNw_sb, void* u0, void* X, void* U, int32_t* status, void* stream) {
+  return mpcb_solve_iterate_pm(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw,
+                               Qw_sb, Rw, Rw_sb, QNw, QNw_sb, nullptr, 0, u0, X, U, status, stream);
 }
 
 // no weight output: the plain kernels, which read neither X nor the references
@@ -1209,8 +1235,8 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
 
 template <class T>
 static int gains_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
-                      const uint8_t* fixed, const void* wind, int64_t wind_sb, void* K, void* P0,
-                      int32_t* status, void* stream) {
+                      const uint8_t* fixed, const void* wind, int64_t wind_sb, const void* model,
+                      int64_t model_sb, void* K, void* P0, int32_t* status, void* stream) {
   const int64_t slot = gains_slot_elems(h->cfg.N);
   if (!h->gains_scratch) {
     // resident slots: mpcb_solve_vjp's count (registers: <= 2 waves per SIMD)
@@ -1242,6 +1268,7 @@ static int gains_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
   a.xbar = (const T*)xbar; a.ubar = (const T*)ubar; a.U = (const T*)U;
   a.fixed = fixed;
   a.wind = (const T*)wind; a.wind_sb = wind_sb;
+  a.model = (const T*)model; a.model_sb = model ? model_sb : 0;
   a.K = (T*)K; a.P0 = (T*)P0;
   a.status = status;
   a.scratch = (T*)h->gains_scratch;
@@ -1279,9 +1306,10 @@ static int gains17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void*
   return MPCB_OK;
 }
 
-extern "C" int mpcb_solve_gains(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
-                                const uint8_t* fixed, const void* wind, int64_t wind_sb, void* K, void* P0,
-                                int32_t* status, void* stream) {
+// mpcb_solve_gains, and with a vehicle record per instance (12/4, checked by the caller) mpcb_solve_gains_pm
+static int gains_entry(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                       const uint8_t* fixed, const void* wind, int64_t wind_sb, const void* model,
+                       int64_t model_sb, void* K, void* P0, int32_t* status, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (h->full && h->cfg.box_x)
     return fail(MPCB_E_UNSUPPORTED, "the gains do not cover the state box (active state rows)");
@@ -1304,8 +1332,23 @@ extern "C" int mpcb_solve_gains(mpcb_handle* h, int64_t B, const void* xbar, con
     return gains17_impl<float>(h, B, xbar, ubar, fixed, K, P0, status, stream);
   }
   if (h->cfg.dtype == MPCB_F64)
-    return gains_impl<double>(h, B, xbar, ubar, U, fixed, wind, wind_sb, K, P0, status, stream);
-  return gains_impl<float>(h, B, xbar, ubar, U, fixed, wind, wind_sb, K, P0, status, stream);
+    return gains_impl<double>(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
+  return gains_impl<float>(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
+}
+
+extern "C" int mpcb_solve_gains(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                                const uint8_t* fixed, const void* wind, int64_t wind_sb, void* K, void* P0,
+                                int32_t* status, void* stream) {
+  return gains_entry(h, B, xbar, ubar, U, fixed, wind, wind_sb, nullptr, 0, K, P0, status, stream);
+}
+
+extern "C" int mpcb_solve_gains_pm(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
+                                   const uint8_t* fixed, const void* wind, int64_t wind_sb, const void* model,
+                                   int64_t model_sb, void* K, void* P0, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance models cover the 12/4 model only (17/6: mpcb_set_params)");
+  if (int rc = check_model_stride(model_sb)) return rc;
+  return gains_entry(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
 }
 
 extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
@@ -1338,6 +1381,32 @@ extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const voi
     e = launch_sim_step<float>(B, (float)T, h->Mf, (const float*)x, (const float*)u, (const float*)wind,
                                wind_sb, (float*)x_out, (hipStream_t)stream);
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_sim_step_pm(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
+                                int64_t wind_sb, const void* model, int64_t model_sb, double T, void* x_out,
+                                void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance models cover the 12/4 model only (17/6: mpcb_set_params)");
+  if (int rc = check_model_stride(model_sb)) return rc;
+  if (!model) return mpcb_sim_step(h, B, x, u, wind, wind_sb, T, x_out, stream);
+  if (B < 0) return fail(MPCB_E_INVALID, "negative batch");
+  if (int rc = check_strides(wind_sb)) return rc;
+  if (B == 0) return MPCB_OK;
+  if (!x || !u || !x_out) return fail(MPCB_E_INVALID, "null array");
+  if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
+  HIP_TRY(hipSetDevice(h->device));
+  hipError_t e;
+  if (h->cfg.dtype == MPCB_F64)
+    e = launch_sim_step_pm<double>(B, T, h->Md.g, (const double*)model, model_sb, (const double*)x,
+                                   (const double*)u, (const double*)wind, wind_sb, (double*)x_out,
+                                   (hipStream_t)stream);
+  else
+    e = launch_sim_step_pm<float>(B, (float)T, h->Mf.g, (const float*)model, model_sb, (const float*)x,
+                                  (const float*)u, (const float*)wind, wind_sb, (float*)x_out,
+                                  (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_pm launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
 

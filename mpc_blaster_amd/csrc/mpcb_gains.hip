@@ -16,8 +16,9 @@
 //  * Pass 2 (backward Riccati): vjp_kernel's stage body without any linear term; lane j < NX
 //    holds column j of K_k and stores it straight to K in [nu, nx] order.  P_0 is stored from its
 //    LDS copy after stage 0.  There is no forward pass.
-// Stores carry no lane-divergent branch: an output nobody asked for, a padding group's and the
-// input lanes' go to a sink in the wave's own workspace slot.
+// Stores to global memory carry no lane-divergent branch: an output nobody asked for, a padding
+// group's and the input lanes' go to a sink in the wave's own workspace slot.  (LDS stores are
+// predicated by lane where a lane owns the data: the rows of P, and with PM the group's model.)
 #include <hip/hip_runtime.h>
 
 #include <limits>
@@ -32,9 +33,18 @@ namespace {
 constexpr int SINK_K = 64 * NU;         // per slot: 16-lane rows of one stage's gains per group
 constexpr int SINK_P = 64 * NX;         // per slot: a row of P_0 per lane
 
-template <class T, int MASK>
+template <class T, int MASK, bool PM>
 __global__ void __launch_bounds__(64) gains_kernel(GainsArgs<T> a) {
   __shared__ GroupLds<T> lds_all[GROUPS];
+  // PM (mpcb_solve_gains_pm): the group's own vehicle, built in pass 1 from its record and kept for
+  // the two passes in LDS (fp64) or in each lane's registers (fp32): pw_kernel's arrangement and
+  // reasons (mpcb_pw.hip); otherwise the handle's
+  constexpr bool PM_LDS = PM && sizeof(T) == 8;
+  Model<T>* Mg = nullptr;
+  if constexpr (PM_LDS) {
+    __shared__ Model<T> m_all[GROUPS];
+    Mg = &m_all[threadIdx.x >> 4];
+  }
   const int lane = threadIdx.x;
   const int q = lane >> 4;
   const int j = lane & 15;
@@ -74,6 +84,16 @@ __global__ void __launch_bounds__(64) gains_kernel(GainsArgs<T> a) {
     uint64_t fix[NU];
 #pragma unroll
     for (int m = 0; m < NU; ++m) fix[m] = 0;
+    Model<T> Mi;   // PM: every lane derives the vehicle (the record's 14 values join the check sum);
+                   // with PM_LDS lane 0 publishes it
+    if constexpr (PM) {
+      model_from_rec<T>(a.model + b * a.model_sb, a.M.g, Mi, chk);
+      if constexpr (PM_LDS) {
+        if (j == 0) *Mg = Mi;
+        __syncthreads();
+      }
+    }
+    const Model<T>& M = PM_LDS ? *Mg : (PM ? Mi : a.M);
     for (int k = j; k < N; k += 16) {
       T xb[NX], ub[NU], xn[NX];
       load_vec<NX>(xbp + (int64_t)k * NX, xb);
@@ -83,7 +103,7 @@ __global__ void __launch_bounds__(64) gains_kernel(GainsArgs<T> a) {
 #pragma unroll
       for (int m = 0; m < NU; ++m) chk += ub[m] * T(0);
       T* cc = CC + ((int64_t)k * GROUPS + q) * LIN_STAGE;
-      rk4_nom<T>(xb, ub, a.h, a.M, w, xn, [&](int stage, const T* c) { store_vec<LIN_N>(cc + stage * LIN_N, c); });
+      rk4_nom<T>(xb, ub, a.h, M, w, xn, [&](int stage, const T* c) { store_vec<LIN_N>(cc + stage * LIN_N, c); });
       if constexpr (MASK) {
         if (a.fixed) {
           const uint8_t* fp = a.fixed + (b * (int64_t)N + k) * NU;
@@ -130,7 +150,7 @@ __global__ void __launch_bounds__(64) gains_kernel(GainsArgs<T> a) {
         for (int i = 0; i < NX; ++i) dx[i] = (j == i) ? T(1) : T(0);
 #pragma unroll
         for (int m = 0; m < NU; ++m) du[m] = (j == NX + m) ? T(1) : T(0);
-        rk4_tan<T>(cc, dx, du, a.h, a.M, col);
+        rk4_tan<T>(cc, dx, du, a.h, M, col);
       }
 #pragma unroll
       for (int i = 0; i < NX; ++i) L.X[j * NX + i] = col[i];
@@ -242,12 +262,17 @@ __global__ void __launch_bounds__(64) gains_kernel(GainsArgs<T> a) {
 
 int64_t gains_slot_elems(int N) { return (int64_t)N * (GROUPS * LIN_STAGE) + SINK_K + SINK_P; }
 
-template <class T> hipError_t launch_gains(const GainsArgs<T>& a, int grid, hipStream_t st) {
+template <class T, bool PM> static hipError_t launch_gains_pm(const GainsArgs<T>& a, int grid, hipStream_t st) {
   if (a.mask)
-    hipLaunchKernelGGL((gains_kernel<T, 1>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((gains_kernel<T, 1, PM>), dim3(grid), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((gains_kernel<T, 0>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((gains_kernel<T, 0, PM>), dim3(grid), dim3(64), 0, st, a);
   return hipGetLastError();
+}
+
+// a.model == NULL: the instantiations of mpcb_solve_gains, whatever the caller
+template <class T> hipError_t launch_gains(const GainsArgs<T>& a, int grid, hipStream_t st) {
+  return a.model ? launch_gains_pm<T, true>(a, grid, st) : launch_gains_pm<T, false>(a, grid, st);
 }
 
 template hipError_t launch_gains<double>(const GainsArgs<double>&, int, hipStream_t);

@@ -237,6 +237,10 @@ template <class T> hipError_t launch_eval(const EvalArgs<T>& a, hipStream_t st);
 template <class T>
 hipError_t launch_sim_step(int64_t B, T h, const Model<T>& M, const T* x, const T* u,
                            const T* wind, int64_t wind_sb, T* xo, hipStream_t st);
+// ... with instance b's vehicle record at model + b * model_sb (mpcb_sim_step_pm; g: the handle's gravity)
+template <class T>
+hipError_t launch_sim_step_pm(int64_t B, T h, T g, const T* model, int64_t model_sb, const T* x,
+                              const T* u, const T* wind, int64_t wind_sb, T* xo, hipStream_t st);
 template <class T>
 hipError_t launch_gen_inputs(int64_t B, int N, T dt, uint64_t seed, uint64_t id_offset,
                              int ref_kind, T* x0, T* xref, int64_t xref_sb, T* uref,

@@ -24,6 +24,43 @@ struct Model {
   T J[9], Jinv[9];
 };
 
+// One instance's vehicle as the caller gives it (MPCB_MODEL_REC in include/mpcb.h):
+//   [0] mass  [1] lx  [2] ly  [3] c  [4] t_blast  [5..13] J row-major
+constexpr int MODEL_REC = 14;
+
+// Model<T> of a record: minv = 1 / mass and Jinv by the adjugate in fp64 from the record's values
+// (the structure of the host's inv3 with one reciprocal of the determinant in place of nine
+// divisions), rounded to T.  Gravity is the handle's.  Every entry adds v * 0 to the check sum of
+// the NaN rule.  The record is the caller's contract (mass > 0, J symmetric positive definite):
+// nothing is validated here.
+template <class T>
+__device__ __forceinline__ void model_from_rec(const T* __restrict__ r, T g, Model<T>& M, T& chk) {
+  T v[MODEL_REC];
+#pragma unroll
+  for (int i = 0; i < MODEL_REC; ++i) { v[i] = r[i]; chk += v[i] * T(0); }
+  M.minv = (T)(1.0 / (double)v[0]);
+  M.g = g;
+  M.lx = v[1];
+  M.ly = v[2];
+  M.c = v[3];
+  M.t_blast = v[4];
+  double A[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { M.J[i] = v[5 + i]; A[i] = (double)v[5 + i]; }
+  const double d = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) +
+                   A[2] * (A[3] * A[7] - A[4] * A[6]);
+  const double id = 1.0 / d;
+  M.Jinv[0] = (T)((A[4] * A[8] - A[5] * A[7]) * id);
+  M.Jinv[1] = (T)((A[2] * A[7] - A[1] * A[8]) * id);
+  M.Jinv[2] = (T)((A[1] * A[5] - A[2] * A[4]) * id);
+  M.Jinv[3] = (T)((A[5] * A[6] - A[3] * A[8]) * id);
+  M.Jinv[4] = (T)((A[0] * A[8] - A[2] * A[6]) * id);
+  M.Jinv[5] = (T)((A[2] * A[3] - A[0] * A[5]) * id);
+  M.Jinv[6] = (T)((A[3] * A[7] - A[4] * A[6]) * id);
+  M.Jinv[7] = (T)((A[1] * A[6] - A[0] * A[7]) * id);
+  M.Jinv[8] = (T)((A[0] * A[4] - A[1] * A[3]) * id);
+}
+
 // sin/cos for the attitude angles: Cody-Waite reduction by pi/2 + fdlibm / Cephes minimax
 // kernels (<= 1-2 ulp for |a| < 2^19).  The library sincos carries a Payne-Hanek large-argument
 // path that costs ~4x the instructions and registers on every call; here it is only the

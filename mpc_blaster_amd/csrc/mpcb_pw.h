@@ -31,6 +31,9 @@ struct PwArgs {
   int32_t* status;
   T* scratch;                        // per-slot workspace (one slot = one wavefront = GROUPS instances)
   int64_t slot_elems;
+  // mpcb_solve_iterate_pm: instance b's vehicle record (MODEL_REC values) at model + b * model_sb;
+  // NULL = the handle's M and the kernels of mpcb_solve_iterate_pw
+  const T* model; int64_t model_sb;
 };
 
 // elements of one workspace slot: the iterate, the captured linearisation scalars and gaps, the

@@ -22,8 +22,15 @@
 //    set update is oracle.ocp.pdas_solve's (full exchange of V with the Kim-Park safeguard,
 //    pbar = 3, and the least-index backup), and passes 2-3 repeat until every group of the wave
 //    has stopped or the cap is reached.  There is no hand-over to an interior point.
-// Stores carry no lane-divergent branch: a padding group's, a stopped group's and those of an
-// output nobody asked for go to a sink in the wave's own workspace slot.
+// Stores to global memory carry no lane-divergent branch: a padding group's, a stopped group's and
+// those of an output nobody asked for go to a sink in the wave's own workspace slot.  (LDS stores
+// are predicated by lane where a lane owns the data: the rows of P, and with PM the group's model.)
+//
+// PM (mpcb_solve_iterate_pm): instance b's vehicle in place of the handle's.  Pass 1 first reads the
+// group's 14-value record, derives minv and Jinv (model_from_rec, mpcb_model.h) and keeps the
+// Model<T> in LDS (fp64: 24 values per group) or in each lane's registers (fp32), where rk4_nom of
+// pass 1 and rk4_tan of passes 2 and 3 read it; the record joins the check sum.  PM = false is the
+// kernel of mpcb_solve_iterate_pw unchanged.
 //
 // NaN rule (mpcb_eval's): every loaded input v adds v * 0 to a check sum, NaN unless v is finite;
 // an instance whose sum is NaN gets status NAN and NaN in every output.  The groups of a wave
@@ -49,10 +56,22 @@ struct PwWeights {
   T QN[NX * NX];
 };
 
-template <class T, int BOX>
+template <class T, int BOX, bool PM>
 __global__ void __launch_bounds__(64) pw_kernel(PwArgs<T> a) {
   __shared__ GroupLds<T> lds_all[GROUPS];
   __shared__ PwWeights<T> w_all[GROUPS];
+  // PM: the group's own vehicle, built in pass 1 from its record (uniform per 16-lane group, not per
+  // wave, so it cannot sit in scalar registers); otherwise the handle's, a kernel argument.  fp64
+  // keeps it in LDS (24 values per group; a copy per lane is 48 registers of a kernel that spills
+  // already, measured: 220 B more scratch per lane).  fp32 has the registers, and every lane keeps
+  // the copy it derives: the tangent's FMAs then read it without an LDS load each, which is the
+  // whole cost of PM there
+  constexpr bool PM_LDS = PM && sizeof(T) == 8;
+  Model<T>* Mg = nullptr;
+  if constexpr (PM_LDS) {
+    __shared__ Model<T> m_all[GROUPS];
+    Mg = &m_all[threadIdx.x >> 4];
+  }
   const int lane = threadIdx.x;
   const int q = lane >> 4;
   const int j = lane & 15;
@@ -88,6 +107,16 @@ __global__ void __launch_bounds__(64) pw_kernel(PwArgs<T> a) {
     const T* ubp = a.ubar + b * (int64_t)N * NU;
 
     // ------------------------------------------------------------------ pass 1: nominal
+    Model<T> Mi;   // PM: the instance's vehicle; every lane derives it (the record's 14 values join
+                   // the check sum), and with PM_LDS lane 0 publishes it for the three passes
+    if constexpr (PM) {
+      model_from_rec<T>(a.model + b * a.model_sb, a.M.g, Mi, chk);
+      if constexpr (PM_LDS) {
+        if (j == 0) *Mg = Mi;
+        __syncthreads();
+      }
+    }
+    const Model<T>& M = PM_LDS ? *Mg : (PM ? Mi : a.M);
     {
       // the instance's weights: 144 + 16 + 144 values over the 16 lanes
       const T* Qp = a.Qw + b * a.Qw_sb;
@@ -116,7 +145,7 @@ __global__ void __launch_bounds__(64) pw_kernel(PwArgs<T> a) {
       store_vec<NX>(XU + (int64_t)k * 64 + q * 16, xb);
       store_vec<NU>(XU + (int64_t)k * 64 + q * 16 + NX, ub);
       T* cc = CC + ((int64_t)k * GROUPS + q) * CC_REC;
-      rk4_nom<T>(xb, ub, a.h, a.M, w, xn, [&](int stage, const T* c) { store_vec<LIN_N>(cc + stage * LIN_N, c); });
+      rk4_nom<T>(xb, ub, a.h, M, w, xn, [&](int stage, const T* c) { store_vec<LIN_N>(cc + stage * LIN_N, c); });
       T gp[NX];
 #pragma unroll
       for (int i = 0; i < NX; ++i) gp[i] = xn[i] - nx[i];
@@ -181,7 +210,7 @@ __global__ void __launch_bounds__(64) pw_kernel(PwArgs<T> a) {
           for (int i = 0; i < NX; ++i) dx[i] = (j == i) ? T(1) : T(0);
 #pragma unroll
           for (int m = 0; m < NU; ++m) du[m] = (j == NX + m) ? T(1) : T(0);
-          rk4_tan<T>(cc, dx, du, a.h, a.M, col);
+          rk4_tan<T>(cc, dx, du, a.h, M, col);
           // gap b = Phi(xbar_k, ubar_k) - xbar_{k+1};  pt = p + P b  (P symmetric: row j = col j)
           T pt = pj;
 #pragma unroll
@@ -386,7 +415,7 @@ __global__ void __launch_bounds__(64) pw_kernel(PwArgs<T> a) {
           if (k == 0) u0p[0] = val;
           const T* cc = CC + ((int64_t)k * GROUPS + q) * CC_REC;
           T dphi[NX];
-          rk4_tan<T>(cc, dxk, duk, a.h, a.M, dphi);
+          rk4_tan<T>(cc, dxk, duk, a.h, M, dphi);
 #pragma unroll
           for (int i = 0; i < NX; ++i) dxk[i] = dphi[i] + cc[LIN_STAGE + i];
         }
@@ -448,17 +477,22 @@ int64_t pw_slot_elems(int N, int box) {
   return (int64_t)(N + 1) * 64 + (int64_t)N * GROUPS * CC_REC + (int64_t)N * 64 * RN + PW_SINK;
 }
 
-template <class T> hipError_t launch_pw(const PwArgs<T>& a, int grid, hipStream_t st) {
+template <class T, bool PM> static hipError_t launch_pw_pm(const PwArgs<T>& a, int grid, hipStream_t st) {
   if constexpr (sizeof(T) == 8) {
     if (a.box) {
-      hipLaunchKernelGGL((pw_kernel<T, 1>), dim3(grid), dim3(64), 0, st, a);
+      hipLaunchKernelGGL((pw_kernel<T, 1, PM>), dim3(grid), dim3(64), 0, st, a);
       return hipGetLastError();
     }
   } else {
     if (a.box) return hipErrorInvalidValue;   // fp32 with the box is refused by the entry point
   }
-  hipLaunchKernelGGL((pw_kernel<T, 0>), dim3(grid), dim3(64), 0, st, a);
+  hipLaunchKernelGGL((pw_kernel<T, 0, PM>), dim3(grid), dim3(64), 0, st, a);
   return hipGetLastError();
+}
+
+// a.model == NULL: the instantiations of mpcb_solve_iterate_pw, whatever the caller
+template <class T> hipError_t launch_pw(const PwArgs<T>& a, int grid, hipStream_t st) {
+  return a.model ? launch_pw_pm<T, true>(a, grid, st) : launch_pw_pm<T, false>(a, grid, st);
 }
 
 template hipError_t launch_pw<double>(const PwArgs<double>&, int, hipStream_t);
