@@ -66,7 +66,8 @@ enum { MPCB_STATUS_OK = 0, MPCB_STATUS_NAN = 1, MPCB_STATUS_MAXITER = 2, MPCB_ST
  * elements of the handle's dtype in a DEVICE array:
  *   [0] mass  [1] lx  [2] ly  [3] c  [4] t_blast  [5..13] J, row-major 3x3
  * Gravity, dt and the boxes stay with the handle.  The entry points that take a record
- * (mpcb_sim_step_pm, mpcb_solve_iterate_pm, mpcb_solve_gains_pm) take it as `model, model_sb`:
+ * (mpcb_sim_step_pm, mpcb_solve_iterate_pm, mpcb_solve_gains_pm, mpcb_sim_step_vjp) take it as
+ * `model, model_sb`:
  *   instance b's record starts at model + b * model_sb, in elements;
  *   model_sb == 0 broadcasts one record; model_sb >= MPCB_MODEL_REC is allowed and the pad elements
  *   are never read; 0 < model_sb < MPCB_MODEL_REC or a negative stride is MPCB_E_INVALID;
@@ -81,8 +82,9 @@ enum { MPCB_STATUS_OK = 0, MPCB_STATUS_NAN = 1, MPCB_STATUS_MAXITER = 2, MPCB_ST
  * Out of scope, each refused or absent: the 17/6 model (its per-instance data are mpcb_set_params);
  * rollout mode (mpcb_solve); the tuned shared-weight solve paths (mpcb_solve_iterate and the bench
  * configs c1-c5 keep one vehicle per handle); mpcb_eval, mpcb_linearize, the mpcb_solve_vjp family
- * and the torch layer at per-instance models; gradients with respect to the model; fp32 with the
- * input box; per-instance gravity, dt or boxes.
+ * and the torch layer at per-instance models; gradients of the RTI step with respect to the model
+ * (the plant step offers the model gradient: mpcb_sim_step_vjp); fp32 with the input box;
+ * per-instance gravity, dt or boxes.
  */
 #define MPCB_MODEL_REC 14
 
@@ -544,6 +546,42 @@ int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const void* u, const
 int mpcb_sim_step_pm(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
                      int64_t wind_sb, const void* model, int64_t model_sb, double T, void* x_out,
                      void* hip_stream);
+
+/*
+ * Reverse mode of the plant step (12/4 model, both dtypes).  With x_out = Phi_b(x, u) the step of
+ * mpcb_sim_step_pm (of mpcb_sim_step when model == NULL) and gxn [B,12] the cotangent of x_out:
+ *   gx     [B,12] = (d x_out / d x)^T gxn
+ *   gu     [B,4]  = (d x_out / d u)^T gxn
+ *   gwind  [B,3]  = (d x_out / d wind)^T gxn
+ *   gmodel [B,14] = (d x_out / d record)^T gxn, in the order of MPCB_MODEL_REC
+ * One sweep back through the four RK4 stages: the exact derivative of the discrete RK4 map, not of
+ * the ODE.
+ *   x, u, wind, wind_sb, model, model_sb, T   by the rules of mpcb_sim_step_pm
+ *   gxn       required
+ *   gx, gu, gwind, gmodel   any may be NULL (not computed), but not all four; contiguous rows,
+ *             element alignment only.  gx may alias gxn (each instance's inputs are read before its
+ *             outputs are written); no other aliasing is allowed.
+ * Broadcast inputs: wind_sb == 0 or model_sb == 0 still gives per-instance gwind / gmodel rows; the
+ * caller sums them (the convention of gQ).  wind == NULL is wind 0, and gwind is still valid.
+ * model == NULL is the handle's vehicle: gmodel is then the gradient at the record equal to the
+ * handle's config, and agrees to rounding with the call given that record broadcast.
+ * gmodel: entry 0 is d/d mass; entries 5..13 are the nine entries of J taken as independent, through
+ * both J and its inverse (gJ - Jinv^T gJinv Jinv^T, that product in fp64), so a symmetric
+ * parametrisation adds (i,j) and (j,i).  No gradient is given with respect to gravity or T.
+ * There is no status, as in mpcb_sim_step_pm: an instance with a non-finite entry in x, u, gxn, its
+ * wind or its record gets NaN in every requested output row; the other instances keep their bits.
+ * No atomics: the same call returns the same bits.
+ * MPCB_E_UNSUPPORTED on a 17/6 handle.  MPCB_E_INVALID: B > max_batch, a missing x, u or gxn, all
+ * four outputs NULL, a negative stride, 0 < model_sb < MPCB_MODEL_REC, T <= 0.  A refused call
+ * writes nothing.
+ */
+int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B,
+                      const void* x, const void* u,
+                      const void* wind, int64_t wind_sb,
+                      const void* model, int64_t model_sb,
+                      double T, const void* gxn,
+                      void* gx, void* gu, void* gwind, void* gmodel,
+                      void* hip_stream);
 
 /*
  * Synthetic inputs (SURVEY §8 d): Philox4x32-10 keyed by (seed, id_offset + i).

@@ -24,7 +24,8 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
            'mpcb_last_timing', 'mpcb_set_params', 'mpcb_set_t_blast', 'mpcb_qp_stats', 'mpcb_poc_jacobians',
            'mpcb_quat_ops', 'mpcb_plan_kernels', 'mpcb_last_kernels', 'mpcb_eval', 'mpcb_solve_vjp',
            'mpcb_solve_vjp_w', 'mpcb_set_weights', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
-           'mpcb_solve_vjp_pw', 'mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm')
+           'mpcb_solve_vjp_pw', 'mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm',
+           'mpcb_sim_step_vjp')
 # the per-instance-model entry points among them (typed after the version check, like the others
 # that joined ABI version 5 without a new number)
 EXPORTS_PM = ('mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm')
@@ -108,7 +109,7 @@ def load(path: str | None = None):
     lib.mpcb_last_kernels.argtypes = [vp, ctypes.c_char_p, i64]
     for name in EXPORTS:
         if name not in ('mpcb_last_error', 'mpcb_workspace_bytes', 'mpcb_solve_gains', 'mpcb_solve_iterate_pw',
-                        'mpcb_solve_vjp_pw') + EXPORTS_PM:
+                        'mpcb_solve_vjp_pw', 'mpcb_sim_step_vjp') + EXPORTS_PM:
             getattr(lib, name).restype = i32
     got = int(lib.mpcb_abi_version())
     if got != ABI_VERSION:
@@ -147,6 +148,11 @@ def load(path: str | None = None):
     lib.mpcb_solve_iterate_pm.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                           vp, i64, vp, i64, vp, vp, vp, vp, vp]
     lib.mpcb_solve_gains_pm.argtypes = [vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp]
+    # (likewise: the reverse mode of the plant step)
+    if not hasattr(lib, 'mpcb_sim_step_vjp'):
+        raise LibraryMissing(f'{p} has no mpcb_sim_step_vjp: rebuild it (__graft_entry__.build())')
+    lib.mpcb_sim_step_vjp.argtypes = [vp, i64, vp, vp, vp, i64, vp, i64, dbl, vp, vp, vp, vp, vp, vp]
+    lib.mpcb_sim_step_vjp.restype = i32
     if path is None:
         _lib = lib
     return lib

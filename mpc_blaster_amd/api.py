@@ -705,6 +705,43 @@ class BatchedMPC:
         self._keep = (xs, us, wd)
         return xo
 
+    def sim_step_vjp(self, x, u, gxn, T=None, wind=None, model=None, want=('gx', 'gu')):
+        """Reverse mode of ``sim_step`` (mpcb_sim_step_vjp; 12/4 model): with ``gxn`` [B,12] the
+        cotangent of the step's output, a dict of device tensors with the keys of ``want``, any
+        non-empty subset of ``gx`` [B,12], ``gu`` [B,4], ``gwind`` [B,3], ``gmodel`` [B,14]
+        (MPCB_MODEL_REC order; entry 0 is d/d mass, the nine entries of J independent).  ``T``,
+        ``wind`` and ``model`` as for ``sim_step``; a broadcast ``wind`` / ``model`` still gives rows
+        per instance, which the caller sums.  Without ``model``, ``gmodel`` is the gradient at the
+        record of the handle's config.  An instance with a non-finite input gets NaN rows."""
+        torch = _torch()
+        if self.nx == 17:
+            raise ValueError('sim_step_vjp covers the 12/4 model only')
+        cols = dict(gx=self.nx, gu=self.nu, gwind=3, gmodel=_lib.MODEL_REC)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or len(set(want)) != len(want) or set(want) - set(cols):
+            raise ValueError(f'want: a non-empty subset of {tuple(cols)}, got {want}')
+        xs, _ = self._dev(x, (self.nx,), 'x')
+        B = xs.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        us, _ = self._dev(u, (self.nu,), 'u', B)
+        gn, _ = self._dev(gxn, (self.nx,), 'gxn', B)
+        wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
+        md, m_sb = (None, 0) if model is None else self._model_arg(model, B)
+        out = {k: torch.empty((B, cols[k]), dtype=self.dtype, device=self._tdev) for k in want}
+        _lib.check(self.lib.mpcb_sim_step_vjp(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(wd), wd_sb,
+                                              self._ptr(md), m_sb, float(self.cfg.dt if T is None else T),
+                                              self._ptr(gn), *(self._ptr(out.get(k)) for k in cols),
+                                              self._stream()))
+        self._keep = (xs, us, gn, wd, md)
+        return out
+
+    def sim_step_diff(self, x, u, T=None, wind=None, model=None):
+        """``sim_step`` as a differentiable torch operation: gradients flow to the tensors ``x``,
+        ``u``, ``wind`` and ``model`` (see ``mpc_blaster_amd.autograd.sim_step_diff``)."""
+        from .autograd import sim_step_diff
+        return sim_step_diff(self, x, u, T=T, wind=wind, model=model)
+
     def gen_inputs(self, B, seed, id_offset=0, ref='hover', wind=False):
         """Synthetic inputs on device (SURVEY §8 d): x0 [B,12], x_ref, u_ref (broadcast for hover)."""
         torch = _torch()

@@ -47,6 +47,16 @@ Each weight tensor receives its gradient per instance in its own shape, the diag
 other than 0 get zeros.  With the input box the solve is the plain active set of
 ``mpcb_solve_iterate_pw`` (fp64 only).  A 17/6 handle raises ``ValueError``.
 
+The plant step.  ``sim_step_diff(mpc, x, u, T=None, wind=None, model=None) -> x_out`` runs
+``BatchedMPC.sim_step`` in the forward pass and one ``mpcb_sim_step_vjp`` call in the backward pass,
+which requests exactly the outputs whose inputs need a gradient: ``x``, ``u``, ``wind`` and ``model``
+(the vehicle records of ``pack_model``).  It is the exact derivative of the discrete RK4 step.  A
+``[1, 3]`` (or ``[3]``) wind and a ``[1, 14]`` (or ``[14]``) model receive the sum over the batch, in
+the tensor's shape and dtype; rows wider than 14 get zeros in the pad columns.  The model gradient
+follows include/mpcb.h: entry 0 is d/d mass, the nine entries of J are independent.  ``T`` and
+gravity carry no gradient.  12/4 model only (a 17/6 handle raises ``ValueError``); not differentiable
+twice.
+
 torch is imported on first use, as in ``api.py``.
 """
 from __future__ import annotations
@@ -172,6 +182,76 @@ def _function():
 
     _FN = SolveIterate
     return _FN
+
+
+_SIM = None
+
+
+def _sim_function():
+    global _SIM
+    if _SIM is not None:
+        return _SIM
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SimStep(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, mpc, x, u, T, wind, model):
+            if mpc.nx == 17:
+                raise ValueError('sim_step_diff covers the 12/4 model only')
+            xs, _ = mpc._dev(x.detach(), (mpc.nx,), 'x')
+            B = xs.shape[0]
+            us, _ = mpc._dev(u.detach(), (mpc.nu,), 'u', B)
+            wd = md = None
+            if wind is not None:
+                wd, _ = mpc._dev(wind.detach() if torch.is_tensor(wind) else wind, (3,), 'wind', B,
+                                 allow_broadcast=True)
+            if model is not None:
+                md, _ = mpc._model_arg(model.detach() if torch.is_tensor(model) else model, B)
+            xo = mpc.sim_step(xs, us, T=T, wind=wd, model=md)
+            ctx.mpc, ctx.T = mpc, T
+            ctx.has = (wd is not None, md is not None)
+            ctx.meta = [(tuple(t.shape), t.dtype) if torch.is_tensor(t) else None for t in (x, u, wind, model)]
+            ctx.save_for_backward(xs, us, *(t for t in (wd, md) if t is not None))
+            return xo
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            mpc = ctx.mpc
+            xs, us = ctx.saved_tensors[:2]
+            rest = list(ctx.saved_tensors[2:])
+            wd = rest.pop(0) if ctx.has[0] else None
+            md = rest.pop(0) if ctx.has[1] else None
+            need = [ctx.needs_input_grad[i] for i in (1, 2, 4, 5)]
+            keys = ('gx', 'gu', 'gwind', 'gmodel')
+            want = tuple(k for k, n in zip(keys, need) if n)
+            grads = [None] * 4
+            if want:
+                out = mpc.sim_step_vjp(xs, us, g.to(mpc.dtype), T=ctx.T, wind=wd, model=md, want=want)
+                for i, k in enumerate(keys):
+                    if k not in out:
+                        continue
+                    shape, dt = ctx.meta[i]
+                    v = out[k]
+                    rows = 1 if len(shape) == 1 else shape[0]
+                    if rows == 1 and v.shape[0] != 1:
+                        v = v.sum(dim=0, keepdim=True)   # one row for the whole batch
+                    if k == 'gmodel' and shape[-1] > v.shape[1]:
+                        v = torch.nn.functional.pad(v, (0, shape[-1] - v.shape[1]))   # pad columns: zeros
+                    grads[i] = v.reshape(shape).to(dt)
+            return (None, grads[0], grads[1], None, grads[2], grads[3])
+
+    _SIM = SimStep
+    return _SIM
+
+
+def sim_step_diff(mpc, x, u, T=None, wind=None, model=None):
+    """x_out [B,12] of ``mpc.sim_step``, differentiable with respect to the torch tensors ``x``, ``u``,
+    ``wind`` and ``model`` (module docstring)."""
+    import torch
+    x, u = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev) for t in (x, u))
+    return _sim_function().apply(mpc, x, u, T, wind, model)
 
 
 def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,

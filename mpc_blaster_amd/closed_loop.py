@@ -156,3 +156,53 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
         x = mpc.sim_step(x, u, T=plant_T, wind=wind, **pkw)
         Xs[:, i + 1] = x
     return Xs, Us, worst
+
+
+def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, wind=None, plant_T=None,
+                     weights=None, plant_model=None, warm_start=True):
+    """The loop of ``closed_loop`` as a differentiable torch operation (12/4 model): returns
+    (X_sim [B, nsim+1, 12], U_sim [B, nsim, 4], status [B] = max over steps).  Each step is
+    ``solve_iterate_diff`` followed by ``sim_step_diff`` (``mpc_blaster_amd.autograd``), so a loss on
+    X_sim, U_sim can be differentiated with respect to the torch tensors ``x0``, ``x_ref``, ``u_ref``,
+    the tensors in ``weights`` and ``plant_model``.  The forward values are ``closed_loop``'s with
+    the same arguments: the same entry points in the same order.
+
+    ``weights``: a dict with any of the keys ``Q``, ``R``, ``QN`` as in ``closed_loop``.  They always go
+    to the solve as per-instance arguments (``per_instance_weights=True``), so a ``[1, n]`` row receives
+    the sum over the batch; installing them on the handle cannot be chained over several steps.
+    ``plant_model``: vehicle records [B|1, 14] of the plant (``sim_step_diff``'s rule for the gradient).
+    ``wind``, ``xbar``, ``ubar`` and the controller's own vehicle are constants; there is no ``model=``
+    argument, because the RTI step's gradients have no per-instance model.
+
+    ``warm_start=True``: the next step linearises at the detached (X, U) of this one, the persistent
+    iterate of ``closed_loop``.  That is the RTI / Gauss-Newton convention: the gradient ignores the
+    path through the iterate.  ``warm_start=False``: every step linearises at the given
+    (``xbar``, ``ubar``); the loop is then piecewise smooth in the differentiated inputs and the
+    gradient is exact on the active sets of the forward pass.  An instance whose solve reports a
+    status other than 0 at some step passes no gradient through that solve."""
+    import torch
+    from .autograd import sim_step_diff, solve_iterate_diff
+    if mpc.nx == 17:
+        raise ValueError('closed_loop_diff covers the 12/4 model only')
+    wkw = {}
+    if weights is not None:
+        unknown = set(weights) - {'Q', 'R', 'QN'}
+        if unknown:
+            raise ValueError(f'weights: unknown keys {sorted(unknown)} (expected Q, R, QN)')
+        wkw = {k: v for k, v in weights.items() if v is not None}
+    dev, dt = f'cuda:{mpc.device}', mpc.dtype
+    x = torch.as_tensor(x0, dtype=dt, device=dev).contiguous()
+    xb = torch.as_tensor(xbar, dtype=dt, device=dev).detach().clone()
+    ub = torch.as_tensor(ubar, dtype=dt, device=dev).detach().clone()
+    worst = torch.zeros((x.shape[0],), dtype=torch.int32, device=dev)
+    Xs, Us = [x], []
+    for _ in range(nsim):
+        u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, wind=wind, per_instance_weights=bool(wkw),
+                                      **wkw)
+        worst = torch.maximum(worst, mpc.get_status())
+        if warm_start:
+            xb, ub = X.detach(), U.detach()
+        x = sim_step_diff(mpc, x, u0, T=plant_T, wind=wind, model=plant_model)
+        Xs.append(x)
+        Us.append(u0)
+    return torch.stack(Xs, dim=1), torch.stack(Us, dim=1), worst

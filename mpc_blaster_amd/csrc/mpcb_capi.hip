@@ -1410,6 +1410,34 @@ extern "C" int mpcb_sim_step_pm(mpcb_handle* h, int64_t B, const void* x, const 
   return MPCB_OK;
 }
 
+extern "C" int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* wind,
+                                 int64_t wind_sb, const void* model, int64_t model_sb, double T, const void* gxn,
+                                 void* gx, void* gu, void* gwind, void* gmodel, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_sim_step_vjp covers the 12/4 model only");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_model_stride(model_sb)) return rc;
+  if (int rc = check_strides(wind_sb)) return rc;
+  if (!gx && !gu && !gwind && !gmodel) return fail(MPCB_E_INVALID, "no output requested");
+  if (B == 0) return MPCB_OK;
+  if (!x || !u || !gxn) return fail(MPCB_E_INVALID, "null array");
+  if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
+  HIP_TRY(hipSetDevice(h->device));
+  hipError_t e;
+  if (h->cfg.dtype == MPCB_F64)
+    e = launch_sim_step_vjp<double>(B, T, h->Md, (const double*)model, model_sb, (const double*)x,
+                                    (const double*)u, (const double*)wind, wind_sb, (const double*)gxn,
+                                    (double*)gx, (double*)gu, (double*)gwind, (double*)gmodel,
+                                    (hipStream_t)stream);
+  else
+    e = launch_sim_step_vjp<float>(B, (float)T, h->Mf, (const float*)model, model_sb, (const float*)x,
+                                   (const float*)u, (const float*)wind, wind_sb, (const float*)gxn, (float*)gx,
+                                   (float*)gu, (float*)gwind, (float*)gmodel, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_vjp launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
 extern "C" int mpcb_gen_inputs(mpcb_handle* h, int64_t B, uint64_t seed, uint64_t id_offset, int ref_kind, void* x0,
                     void* xref, int64_t xref_sb, void* uref, int64_t uref_sb, void* wind, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");

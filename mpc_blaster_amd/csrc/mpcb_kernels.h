@@ -241,6 +241,12 @@ hipError_t launch_sim_step(int64_t B, T h, const Model<T>& M, const T* x, const 
 template <class T>
 hipError_t launch_sim_step_pm(int64_t B, T h, T g, const T* model, int64_t model_sb, const T* x,
                               const T* u, const T* wind, int64_t wind_sb, T* xo, hipStream_t st);
+// mpcb_sim_step_vjp (mpcb_simvjp.hip): the reverse sweep of either plant step.  model null: the
+// vehicle is M; otherwise instance b's record at model + b * model_sb with M.g.  Any output may be null.
+template <class T>
+hipError_t launch_sim_step_vjp(int64_t B, T h, const Model<T>& M, const T* model, int64_t model_sb,
+                               const T* x, const T* u, const T* wind, int64_t wind_sb, const T* gxn,
+                               T* gx, T* gu, T* gwind, T* gmodel, hipStream_t st);
 template <class T>
 hipError_t launch_gen_inputs(int64_t B, int N, T dt, uint64_t seed, uint64_t id_offset,
                              int ref_kind, T* x0, T* xref, int64_t xref_sb, T* uref,

@@ -506,4 +506,156 @@ __device__ __forceinline__ void rk4_tan(const T* __restrict__ C, const T* __rest
   rk4_tan_g<T, FENCE>([&](int i) { return C[i * cs]; }, dx, du, h, M, dxn);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reverse mode of the same split (mpcb_sim_step_vjp).  ``f_adj_lin`` is the transpose of
+// ``f_tan_lin``: from one stage's captured scalars and an adjoint ``a`` of f it accumulates
+// J_f^T a into (px, pu) and, with WM, the adjoints of the model quantities f reads.
+// ---------------------------------------------------------------------------------------------
+// Adjoints of what f reads of Model<T> and of the wind (gravity has none: it is the handle's).
+template <class T>
+struct ModelAdj {
+  T minv, t_blast, lx, ly, c;
+  T J[9], Jinv[9], w[3];
+  __device__ __forceinline__ void zero() {
+    minv = t_blast = lx = ly = c = T(0);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { J[i] = T(0); Jinv[i] = T(0); }
+    w[0] = w[1] = w[2] = T(0);
+  }
+};
+
+// px += (df/dx)^T a, pu += (df/du)^T a, G += (df/dtheta)^T a (WM) at the stage whose scalars are c.
+// No transcendental, no division.  The moment vector m = Mom(u) - w x J w, which only the adjoint
+// of Jinv needs, is recomputed from u and the captured J w, w (same expressions as f_nom_lin).
+template <class T, bool WM>
+__device__ __forceinline__ void f_adj_lin(const T* __restrict__ c, const T* __restrict__ u,
+                                          const Model<T>& M, const T w[3], const T* __restrict__ a,
+                                          T* __restrict__ px, T* __restrict__ pu, ModelAdj<T>& G) {
+  const T sf = c[0], cf = c[1], st = c[2], ct = c[3], sp = c[4], cp = c[5], ict = c[6], tt = c[7];
+  const T av = c[8], cfst = c[9], s = c[10], r0 = c[11], r1 = c[12], r2 = c[13];
+  const T jw0 = c[14], jw1 = c[15], jw2 = c[16], wx = c[17], wy = c[18], wz = c[19];
+  // ---- p_dot = v
+  px[6] += a[0]; px[7] += a[1]; px[8] += a[2];
+  // ---- eta_dot: f3 = wx + tt A, f4 = b, f5 = A ict;  A = sf wy + cf wz, b = cf wy - sf wz
+  const T gA = tt * a[3] + ict * a[5];
+  const T gtt = av * a[3];
+  const T gict = av * a[5] + st * gtt;
+  T gst = ict * gtt;
+  T gct = -(ict * ict) * gict;
+  T gsf = wy * gA - wz * a[4];
+  T gcf = wz * gA + wy * a[4];
+  T gwx = a[3];
+  T gwy = sf * gA + cf * a[4];
+  T gwz = cf * gA - sf * a[4];
+  // ---- v_dot: f6..8 = r s + w minv (- g),  s = Ttot minv
+  const T gr0 = s * a[6], gr1 = s * a[7], gr2 = s * a[8];
+  const T gs = r0 * a[6] + r1 * a[7] + r2 * a[8];
+  const T gT = M.minv * gs;
+  const T gcfst = cp * gr0 + sp * gr1;
+  const T gcp = cfst * gr0 - sf * gr1;
+  const T gsp = sf * gr0 + cfst * gr1;
+  gsf += sp * gr0 - cp * gr1;
+  gcf += ct * gr2 + st * gcfst;
+  gct += cf * gr2;
+  gst += cf * gcfst;
+  px[3] += cf * gsf - sf * gcf;
+  px[4] += ct * gst - st * gct;
+  px[5] += cp * gsp - sp * gcp;
+  // ---- omega_dot = Jinv m,  m = Mom(u) - w x J w
+  const T gm0 = M.Jinv[0] * a[9] + M.Jinv[3] * a[10] + M.Jinv[6] * a[11];
+  const T gm1 = M.Jinv[1] * a[9] + M.Jinv[4] * a[10] + M.Jinv[7] * a[11];
+  const T gm2 = M.Jinv[2] * a[9] + M.Jinv[5] * a[10] + M.Jinv[8] * a[11];
+  const T e0 = M.ly * gm0, e1 = M.lx * gm1, e2 = M.c * gm2;
+  pu[0] += gT - e0 - e1 - e2;
+  pu[1] += gT + e0 + e1 - e2;
+  pu[2] += gT - e0 + e1 + e2;
+  pu[3] += gT + e0 - e1 + e2;
+  // c = w x J w enters m with a minus sign: gc = -gm
+  gwx += jw2 * gm1 - jw1 * gm2;
+  gwy += jw0 * gm2 - jw2 * gm0;
+  gwz += jw1 * gm0 - jw0 * gm1;
+  const T gj0 = wy * gm2 - wz * gm1;
+  const T gj1 = wz * gm0 - wx * gm2;
+  const T gj2 = wx * gm1 - wy * gm0;
+  px[9] += gwx + M.J[0] * gj0 + M.J[3] * gj1 + M.J[6] * gj2;
+  px[10] += gwy + M.J[1] * gj0 + M.J[4] * gj1 + M.J[7] * gj2;
+  px[11] += gwz + M.J[2] * gj0 + M.J[5] * gj1 + M.J[8] * gj2;
+  if constexpr (WM) {
+    const T Ttot = (u[0] + u[1]) + (u[2] + u[3]) + M.t_blast;
+    G.minv += Ttot * gs + w[0] * a[6] + w[1] * a[7] + w[2] * a[8];
+    G.t_blast += gT;
+    G.w[0] += M.minv * a[6]; G.w[1] += M.minv * a[7]; G.w[2] += M.minv * a[8];
+    const T d0 = u[1] + u[3] - u[0] - u[2];
+    const T d1 = u[1] + u[2] - u[0] - u[3];
+    const T d2 = u[2] + u[3] - u[0] - u[1];
+    G.ly += d0 * gm0; G.lx += d1 * gm1; G.c += d2 * gm2;
+    G.J[0] += gj0 * wx; G.J[1] += gj0 * wy; G.J[2] += gj0 * wz;
+    G.J[3] += gj1 * wx; G.J[4] += gj1 * wy; G.J[5] += gj1 * wz;
+    G.J[6] += gj2 * wx; G.J[7] += gj2 * wy; G.J[8] += gj2 * wz;
+    const T m0 = d0 * M.ly - (wy * jw2 - wz * jw1);
+    const T m1 = d1 * M.lx - (wz * jw0 - wx * jw2);
+    const T m2 = d2 * M.c - (wx * jw1 - wy * jw0);
+    G.Jinv[0] += a[9] * m0; G.Jinv[1] += a[9] * m1; G.Jinv[2] += a[9] * m2;
+    G.Jinv[3] += a[10] * m0; G.Jinv[4] += a[10] * m1; G.Jinv[5] += a[10] * m2;
+    G.Jinv[6] += a[11] * m0; G.Jinv[7] += a[11] * m1; G.Jinv[8] += a[11] * m2;
+  }
+}
+
+// Reverse sweep of rk4_nom: lam is the cotangent of xn; C holds the 4 stages' captured scalars
+// (LIN_STAGE values, stage-major).  gx = (dPhi/dx)^T lam, gu = (dPhi/du)^T lam, G the model part:
+//   a4 = h/6 lam,              p4 = J_f(X4)^T a4
+//   a3 = h/3 lam + h   p4.x,   p3 = J_f(X3)^T a3
+//   a2 = h/3 lam + h/2 p3.x,   p2 = J_f(X2)^T a2
+//   a1 = h/6 lam + h/2 p2.x,   p1 = J_f(X1)^T a1
+//   gx = lam + sum pi.x, gu = sum pi.u, G = sum pi.theta
+template <class T, bool WM>
+__device__ __forceinline__ void rk4_adj(const T* __restrict__ C, const T* __restrict__ u, T h,
+                                        const Model<T>& M, const T w[3], const T* __restrict__ lam,
+                                        T* __restrict__ gx, T* __restrict__ gu, ModelAdj<T>& G) {
+  constexpr int NX = 12;
+  const T h2 = T(0.5) * h, h6 = h / T(6), h3 = h / T(3);
+  T a[NX], p[NX];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) gu[m] = T(0);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) { gx[i] = lam[i]; a[i] = h6 * lam[i]; p[i] = T(0); }
+  f_adj_lin<T, WM>(C + 3 * LIN_N, u, M, w, a, p, gu, G);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) { gx[i] += p[i]; a[i] = h3 * lam[i] + h * p[i]; p[i] = T(0); }
+  f_adj_lin<T, WM>(C + 2 * LIN_N, u, M, w, a, p, gu, G);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) { gx[i] += p[i]; a[i] = h3 * lam[i] + h2 * p[i]; p[i] = T(0); }
+  f_adj_lin<T, WM>(C + LIN_N, u, M, w, a, p, gu, G);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) { gx[i] += p[i]; a[i] = h6 * lam[i] + h2 * p[i]; p[i] = T(0); }
+  f_adj_lin<T, WM>(C, u, M, w, a, p, gu, G);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) gx[i] += p[i];
+}
+
+// From the model adjoints to the record (MPCB_MODEL_REC order):
+//   [0] d/d mass = -minv^2 g_minv   [1..4] lx, ly, c, t_blast
+//   [5..13] gJ - Jinv^T gJinv Jinv^T (J's nine entries independent, through J and its inverse);
+// that product in fp64, rounded to T, as model_from_rec forms Jinv.
+template <class T>
+__device__ __forceinline__ void model_adj_to_rec(const Model<T>& M, const ModelAdj<T>& G,
+                                                 T* __restrict__ r) {
+  r[0] = -(M.minv * M.minv) * G.minv;
+  r[1] = G.lx; r[2] = G.ly; r[3] = G.c; r[4] = G.t_blast;
+  double t[9];   // t = Jinv^T gJinv
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      t[i * 3 + j] = (double)M.Jinv[i] * (double)G.Jinv[j] + (double)M.Jinv[3 + i] * (double)G.Jinv[3 + j] +
+                     (double)M.Jinv[6 + i] * (double)G.Jinv[6 + j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)   // (t Jinv^T)_ij = sum_k t_ik Jinv_jk
+      r[5 + i * 3 + j] = (T)((double)G.J[i * 3 + j] - (t[i * 3] * (double)M.Jinv[j * 3] +
+                                                       t[i * 3 + 1] * (double)M.Jinv[j * 3 + 1] +
+                                                       t[i * 3 + 2] * (double)M.Jinv[j * 3 + 2]));
+}
+
 }  // namespace mpcb
