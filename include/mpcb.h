@@ -659,6 +659,11 @@ int mpcb_poc_jacobians(int64_t B, const double* pose, double stream_velocity, co
  * ``out[2b+1]`` = polish passes (fp64 state box).  ``out`` is a DEVICE int32 array [B, 2], B <= that
  * solve's batch.  Reference counterpart: HPIPM's ``get_stats('qp_iter')``.  MPCB_E_UNSUPPORTED on
  * handles without an input box.
+ * "The last solve" is the last accepted mpcb_solve or mpcb_solve_iterate: no other entry point
+ * writes the statistics, so they survive any number of later calls of the others.  In particular
+ * a boxed mpcb_solve_iterate_pw or mpcb_solve_iterate_pm does not count as a solve here: its
+ * active set keeps no statistics, and a read after it still returns those of the last
+ * mpcb_solve / mpcb_solve_iterate, for at most that solve's batch (tests/test_gpu_history.py).
  */
 int mpcb_qp_stats(mpcb_handle* h, int64_t B, int32_t* out, void* hip_stream);
 

@@ -45,6 +45,8 @@ class BatchedMPC:
         self._u0 = self._X = self._U = self._status = None
         self._params = None
         self._weights_version = 0   # bumped by set_weights (autograd checks it in backward)
+        self._model_version = 0     # bumped by set_t_blast and set_params (likewise)
+        self._model_setter = None   # ... and the name of the one that moved it last
 
     # ------------------------------------------------------------------ helpers
     def close(self):
@@ -111,16 +113,19 @@ class BatchedMPC:
         return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
 
     def _outputs(self, B, want_traj):
+        """Fresh (u0, X, U, status) for a solve.  The caller installs them as the handle's last
+        solve only once the library has accepted the call, so a refused solve leaves
+        ``get_control()`` and the others at the previous solve's tensors."""
         torch = _torch()
         dev = self._tdev
         N = self.cfg.N
-        self._u0 = torch.empty((B, self.nu), dtype=self.dtype, device=dev)
-        self._status = torch.empty((B,), dtype=torch.int32, device=dev)
+        u0 = torch.empty((B, self.nu), dtype=self.dtype, device=dev)
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+        X = U = None
         if want_traj:
-            self._X = torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev)
-            self._U = torch.empty((B, N, self.nu), dtype=self.dtype, device=dev)
-        else:
-            self._X = self._U = None
+            X = torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev)
+            U = torch.empty((B, N, self.nu), dtype=self.dtype, device=dev)
+        return u0, X, U, status
 
     @staticmethod
     def _ptr(t):
@@ -226,15 +231,13 @@ class BatchedMPC:
         xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
         ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
         wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
-        if out is None:
-            self._outputs(B, want_traj)
-        else:
-            self._u0, self._X, self._U, self._status = out
-        self._keep = (x0, xr, ur, wd)
+        u0, X, U, status = self._outputs(B, want_traj) if out is None else out
+        keep = (x0, xr, ur, wd)
         _lib.check(self.lib.mpcb_solve(
             self._h, B, self._ptr(x0), self.nx, self._ptr(xr), xr_sb, self._ptr(ur), ur_sb,
-            self._ptr(wd), wd_sb, self._ptr(self._u0), self._ptr(self._X), self._ptr(self._U),
-            self._ptr(self._status), self._stream()))
+            self._ptr(wd), wd_sb, self._ptr(u0), self._ptr(X), self._ptr(U), self._ptr(status), self._stream()))
+        self._keep = keep
+        self._u0, self._X, self._U, self._status = u0, X, U, status
         return self._u0
 
     def solve_iterate(self, x0, xbar, ubar, x_ref, u_ref, wind=None, out=None, Q=None, R=None, QN=None,
@@ -260,38 +263,38 @@ class BatchedMPC:
         xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
         ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
         wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
-        if out is None:
-            self._outputs(B, True)
-        else:
-            self._u0, self._X, self._U, self._status = out
+        u0, X, U, status = self._outputs(B, True) if out is None else out
         if model is not None:
             if B > self.max_batch:
                 raise ValueError(f'batch {B} > max_batch {self.max_batch}')
             md, m_sb = self._model_arg(model, B)
             (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN)
-            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd, md)
             _lib.check(self.lib.mpcb_solve_iterate_pm(
                 self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
                 self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb,
-                self._ptr(QNd), QN_sb, self._ptr(md), m_sb, self._ptr(self._u0), self._ptr(self._X),
-                self._ptr(self._U), self._ptr(self._status), self._stream()))
+                self._ptr(QNd), QN_sb, self._ptr(md), m_sb, self._ptr(u0), self._ptr(X), self._ptr(U),
+                self._ptr(status), self._stream()))
+            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd, md)
+            self._u0, self._X, self._U, self._status = u0, X, U, status
             return self._u0
         if Q is not None or R is not None or QN is not None:
             if B > self.max_batch:
                 raise ValueError(f'batch {B} > max_batch {self.max_batch}')
             (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN)
-            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd)
             _lib.check(self.lib.mpcb_solve_iterate_pw(
                 self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
                 self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb,
-                self._ptr(QNd), QN_sb, self._ptr(self._u0), self._ptr(self._X), self._ptr(self._U),
-                self._ptr(self._status), self._stream()))
+                self._ptr(QNd), QN_sb, self._ptr(u0), self._ptr(X), self._ptr(U), self._ptr(status),
+                self._stream()))
+            self._keep = (x0, xb, ub, xr, ur, wd, Qd, Rd, QNd)
+            self._u0, self._X, self._U, self._status = u0, X, U, status
             return self._u0
-        self._keep = (x0, xb, ub, xr, ur, wd)
         _lib.check(self.lib.mpcb_solve_iterate(
             self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
-            self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(self._u0), self._ptr(self._X),
-            self._ptr(self._U), self._ptr(self._status), self._stream()))
+            self._ptr(ur), ur_sb, self._ptr(wd), wd_sb, self._ptr(u0), self._ptr(X), self._ptr(U),
+            self._ptr(status), self._stream()))
+        self._keep = (x0, xb, ub, xr, ur, wd)
+        self._u0, self._X, self._U, self._status = u0, X, U, status
         return self._u0
 
     def evaluate(self, X, U, x_ref, u_ref, x0=None, wind=None, stat=True):
@@ -600,12 +603,17 @@ class BatchedMPC:
 
         Shapes: [25] or [B|1, 25] (every stage alike), or [B|1, N|N+1, 25] stage by stage (the
         terminal stage N has no dynamics; its row is ignored).  ``None`` restores the defaults
-        (zeros, T_blast = ``config.t_blast`` / ``set_t_blast``)."""
+        (zeros, T_blast = ``config.t_blast`` / ``set_t_blast``).
+
+        An accepted call bumps ``_model_version``: the backward pass of a ``solve_iterate_diff``
+        whose forward pass ran before it raises ``RuntimeError`` (``mpc_blaster_amd.autograd``)."""
         if self.nx != 17:
             raise ValueError('set_params is for the 17/6 model; the 12/4 slice takes set_t_blast')
         if p is None:
-            self._params = None
             _lib.check(self.lib.mpcb_set_params(self._h, 0, ctypes.c_void_p(0), 0, 0))
+            self._params = None
+            self._model_version += 1
+            self._model_setter = 'set_params'
             return
         torch = _torch()
         N = self.cfg.N
@@ -621,18 +629,24 @@ class BatchedMPC:
         # acados ``set`` copies: a private device copy, so later writes to the caller's tensor
         # do not reach the solver (the library reads the pointer at every solve, mpcb.h)
         t = t.contiguous().clone()
-        self._params = t   # the library keeps the device pointer: hold the tensor
         rows, stages = t.shape[0], t.shape[1]
         sb = 0 if rows == 1 else stages * 25
         kb = 0 if stages == 1 else 25
         _lib.check(self.lib.mpcb_set_params(self._h, rows, self._ptr(t), sb, kb))
+        self._params = t   # the library keeps the device pointer: hold the tensor
+        self._model_version += 1
+        self._model_setter = 'set_params'
 
     def set_t_blast(self, t_blast: float):
         """Blaster thrust p[24] (blastermodel.py:210) as a scalar for every instance and stage:
         the 12/4 slice's body-z force; on the 17/6 model the default parameter vector's T_blast.
-        Updates the handle in place (no re-creation)."""
+        Updates the handle in place (no re-creation).  Bumps ``_model_version``: the backward pass
+        of a ``solve_iterate_diff``, or of a ``sim_step_diff`` without a ``model`` record, whose
+        forward pass ran before it raises ``RuntimeError`` (``mpc_blaster_amd.autograd``)."""
         _lib.check(self.lib.mpcb_set_t_blast(self._h, float(t_blast)))
         self.cfg.t_blast = float(t_blast)
+        self._model_version += 1
+        self._model_setter = 'set_t_blast'
 
     def qp_stats(self, B=None):
         """Input-box work statistics of the last solve: int32 [B, 2] device tensor per instance

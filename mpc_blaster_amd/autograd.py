@@ -32,10 +32,19 @@ on the host (a synchronisation) and waits for the device, and the handle keeps t
 afterwards.  The backward pass returns, for each weight tensor, the gradient summed over the
 instances with forward status 0, in the tensor's shape and dtype: the symmetric matrix gQ of
 include/mpcb.h for a matrix (so that dL = <gQ, dQ> for a symmetric dQ), its diagonal for a vector.
-It is exact on the active set at fixed (xbar, ubar), like the others.  The backward pass needs the
-weights the forward pass solved with: it raises ``RuntimeError`` if ``set_weights`` (or another
-forward pass with weight tensors) has changed the handle's weights in between.  Without weight
-arguments nothing of this applies and the layer is as before.
+It is exact on the active set at fixed (xbar, ubar), like the others.
+
+Handle state between forward and backward.  Every gradient of the step, ``x0``'s, ``x_ref``'s and
+``u_ref``'s as much as the weights', is taken at the handle's Q, R, QN and vehicle, which the
+backward pass reads from the handle when it runs.  Every forward pass therefore records the
+handle's weights version and its model version (``BatchedMPC._weights_version``, bumped by
+``set_weights``, hence also by another forward pass with weight tensors; ``_model_version``, bumped
+by ``set_t_blast`` and ``set_params``), with or without weight arguments, and the backward pass
+raises ``RuntimeError`` naming the setter if either has moved: it never returns the gradient of a
+problem the forward pass did not solve.  A comparison is left out exactly where the backward pass
+does not read that state: the weights version with per-instance weights when all three of ``Q``,
+``R``, ``QN`` are given (an omitted one falls back to the handle's), the model version in the plant
+step with a ``model`` record.  Restore nothing by hand: run the forward pass again.
 
 Weights per instance (``per_instance_weights=True``, 12/4 model).  ``Q``, ``R``, ``QN`` then carry a
 batch axis: a 2-D tensor ``[B|1, n]`` holds diagonals, a 3-D tensor ``[B|1, n, n]`` symmetric
@@ -54,7 +63,9 @@ which requests exactly the outputs whose inputs need a gradient: ``x``, ``u``, `
 ``[1, 3]`` (or ``[3]``) wind and a ``[1, 14]`` (or ``[14]``) model receive the sum over the batch, in
 the tensor's shape and dtype; rows wider than 14 get zeros in the pad columns.  The model gradient
 follows include/mpcb.h: entry 0 is d/d mass, the nine entries of J are independent.  ``T`` and
-gravity carry no gradient.  12/4 model only (a 17/6 handle raises ``ValueError``); not differentiable
+gravity carry no gradient.  Without ``model`` the step is the handle's vehicle's, so ``set_t_blast``
+between forward and backward raises ``RuntimeError`` (above); with a record it goes through.  12/4
+model only (a 17/6 handle raises ``ValueError``); not differentiable
 twice.
 
 torch is imported on first use, as in ``api.py``.
@@ -62,6 +73,19 @@ torch is imported on first use, as in ``api.py``.
 from __future__ import annotations
 
 _FN = None
+
+
+def _same_weights(mpc, version):
+    if mpc._weights_version != version:
+        raise RuntimeError('the weights of the MPC handle changed after the forward pass (set_weights, or '
+                           'another forward pass with weight tensors): every gradient of the step needs the '
+                           'weights the forward pass solved with')
+
+
+def _same_model(mpc, version):
+    if mpc._model_version != version:
+        raise RuntimeError(f'{mpc._model_setter} changed the vehicle of the MPC handle after the forward pass: '
+                           'the gradient needs the model the forward pass ran with')
 
 
 def _function():
@@ -112,9 +136,10 @@ def _function():
             ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
             ctx.has_wind = wd is not None
             saved = [xb, ub, U, status] + ([wd] if wd is not None else [])
+            # the handle state the backward pass will read again (module docstring)
+            ctx.wversion, ctx.mversion = mpc._weights_version, mpc._model_version
             if ctx.has_weights:
                 ctx.wmeta = [None if w is None else (tuple(w.shape), w.dtype) for w in wts]
-                ctx.wversion = mpc._weights_version
                 saved += [X, x_ref.detach(), u_ref.detach()]
             if ctx.pw:
                 ctx.wpresent = [w is not None for w in wdet]
@@ -131,6 +156,9 @@ def _function():
             need = ctx.needs_input_grad
             kw = dict(fixed=ctx.fixed) if ctx.full else dict(wind=wd)
             want_w = ctx.has_weights and any(need[7:10])
+            if not (ctx.pw and all(ctx.wpresent)):
+                _same_weights(mpc, ctx.wversion)
+            _same_model(mpc, ctx.mversion)
             gU = g_U.to(mpc.dtype).clone()
             gU[:, 0] += g_u0.to(mpc.dtype)
             pwkw = {}
@@ -146,10 +174,6 @@ def _function():
             elif ctx.pw:
                 out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, wind=wd, **pwkw)
             elif want_w:
-                if mpc._weights_version != ctx.wversion:
-                    raise RuntimeError('the weights of the MPC handle changed after the forward pass '
-                                       '(set_weights or another forward with weight tensors): the '
-                                       'weight gradient needs the weights the forward solved with')
                 X, xr, ur = ctx.saved_tensors[-3:]
                 out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=U, X=X, x_ref=xr, u_ref=ur, weights=True,
                                             **kw)
@@ -210,6 +234,7 @@ def _sim_function():
                 md, _ = mpc._model_arg(model.detach() if torch.is_tensor(model) else model, B)
             xo = mpc.sim_step(xs, us, T=T, wind=wd, model=md)
             ctx.mpc, ctx.T = mpc, T
+            ctx.mversion = mpc._model_version   # read again by the backward pass unless a record is given
             ctx.has = (wd is not None, md is not None)
             ctx.meta = [(tuple(t.shape), t.dtype) if torch.is_tensor(t) else None for t in (x, u, wind, model)]
             ctx.save_for_backward(xs, us, *(t for t in (wd, md) if t is not None))
@@ -228,6 +253,8 @@ def _sim_function():
             want = tuple(k for k, n in zip(keys, need) if n)
             grads = [None] * 4
             if want:
+                if md is None:
+                    _same_model(mpc, ctx.mversion)
                 out = mpc.sim_step_vjp(xs, us, g.to(mpc.dtype), T=ctx.T, wind=wd, model=md, want=want)
                 for i, k in enumerate(keys):
                     if k not in out:

@@ -485,9 +485,18 @@ def test_torch_layer_refuses_stale_weights():
     m.set_weights(Q=2.0 * q)
     with pytest.raises(RuntimeError, match='weights'):
         X.sum().backward()
-    # without weight arguments the layer does not look at the version
+    # without weight arguments x0's gradient still depends on Q, R and QN: the same refusal
     x0 = _t(c['x0'], True)
     u0, X, U = m.solve_iterate_diff(x0, c['xbar'], c['ubar'], c['xref'], c['uref'])
     m.set_weights(Q=q)
+    with pytest.raises(RuntimeError, match='weights'):
+        X.sum().backward()
+    assert x0.grad is None
+    # the control: the same forward and backward with nothing in between, against the reference
+    # (the handle holds the default Q again)
+    u0, X, U = m.solve_iterate_diff(x0, c['xbar'], c['ubar'], c['xref'], c['uref'])
     X.sum().backward()
-    assert x0.grad is not None
+    from vjp_ref import vjp_ref
+    ref = vjp_ref(c['xbar'], c['ubar'], None, np.ones((B, N + 1, 12)), None, OcpSpec(N=N))
+    assert (m.get_status() == 0).all()
+    assert relerr(x0.grad.cpu().numpy(), ref['gx0']).max() <= BOUND['f64']
