@@ -688,6 +688,7 @@ __device__ __forceinline__ void as_body(const SplitArgs<T>& args) {
   int kc = -1;                  // highest stage whose active set changed (group-uniform)
   int git = 0;                  // passes of the group's current instance
   int rpass = 0;                // REF: refined passes of the group's current instance
+  int git0 = 0;                 // REF: the listed pass count (the refinement's own budget counts from it)
   M relm = 0, pin = 0;          // REF, input lanes: stages released by the refinement; fixed again after
   M lrel = 0;                   // REF, input lanes: the releases the last refined pass applied
   // REF: the listed instance's active set and counts (as_ref_put), and its U (the output the
@@ -701,7 +702,7 @@ __device__ __forceinline__ void as_body(const SplitArgs<T>& args) {
         const T* const ub = a.U + b * (int64_t)N * NU;
         for (int e = j; e < N * NU; e += NZ) us0[e] = ub[e];
         wave_lds_sync();
-        git = ent[1];
+        git = git0 = ent[1];
         n_fwd = ent[2];
         n_bst = ent[3];
         kc = ent[AS_REF_KC];   // (an interior-point instance: the full backward pass first)
@@ -1341,8 +1342,15 @@ __device__ __forceinline__ void as_body(const SplitArgs<T>& args) {
     // (or, with the fallback, the first pass violates more than 7/20 of the horizon's input
     // components: oracle.ocp.AS_IPM_NV_NUM / _DEN, a strongly constrained QP)
     const bool crowded = BOX && a.as_fb && git == 0 && nV * AS_IPM_NV_DEN > AS_IPM_NV_NUM * N * NU;
-    const bool fin_now = write && (cvd || git + 1 >= a.max_as_iter || crowded);
-    if (stage_out && fin_now) flush_out();
+    // (the refinement kernel: AS_REF_BUDGET refined passes from the listed count on, whatever
+    // max_as_iter is -- under the active set's cap an instance listed at its last allowed pass,
+    // or a hand-over at max_as_iter <= 2, got one refined pass and ended as MAXITER when that
+    // pass changed the set: tests/test_gpu_pass_cap.py)
+    const bool capped = REF ? git - git0 + 1 >= AS_REF_BUDGET : git + 1 >= a.max_as_iter;
+    const bool fin_now = write && (cvd || capped || crowded);
+    // (... and out of budget it leaves the instance as the earlier kernel finished it: that
+    // kernel's outputs and its status)
+    if (stage_out && fin_now && (!REF || cvd)) flush_out();
     wave_lds_sync();   // the next pass's staging writes follow the flush's LDS reads
     ++git;
     if (fin_now) {
@@ -1352,7 +1360,7 @@ __device__ __forceinline__ void as_body(const SplitArgs<T>& args) {
       const bool to_ipm = BOX && !REF && !cvd && st == MPCB_STATUS_OK && a.as_fb;
       if (to_ipm) {
         if (j == 0) a.as_fb[2 + atomicAdd(a.as_fb, 1)] = (int)c;
-      } else if (!cvd) {
+      } else if (!cvd && !REF) {
         st = (st == MPCB_STATUS_OK) ? MPCB_STATUS_MAXITER : st;
       }
       if constexpr (UNC && !REF) {

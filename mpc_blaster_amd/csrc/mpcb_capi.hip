@@ -434,7 +434,7 @@ static hipError_t upload_weights(mpcb_handle* h, const mpcb_config& c) {
   return hipMemcpy(h->weights, &w, sizeof(w), hipMemcpyHostToDevice);
 }
 
-// the fp32 refinement list's capacity: the whole batch (c4 lists 252 of 65,536, but on strongly
+// the fp32 refinement list's capacity: the whole batch (c4 lists 667-682 of 65,536, but on strongly
 // constrained draws most instances reach it through the interior-point fallback)
 static int64_t ref_cap(int64_t max_batch) { return max_batch; }
 
@@ -527,9 +527,12 @@ extern "C" int mpcb_debug_set_as_order(mpcb_handle* h, const int32_t* dev_order)
 #endif
 // Diagnostic (not part of the ABI header): the last fp32 input-box chunk's refinement list header
 // (mpcb_kernels.h AS_REF_*: [0] instances listed, [1] the refinement kernel's counter), read
-// synchronously into out[0..1] (tools/c4_full_parity.py).
+// synchronously into out[0..1] (tools/c4_full_parity.py).  Only a 12/4 fp32 input-box handle has
+// the list: on a 17/6 or an fp64 handle nothing ever initialises that region.
 extern "C" int mpcb_debug_ref_list(mpcb_handle* h, int32_t* out) {
   if (!h || !h->qp_stats || !out) return fail(MPCB_E_INVALID, "no input-box handle");
+  if (h->full || h->cfg.dtype != MPCB_F32)
+    return fail(MPCB_E_UNSUPPORTED, "the refinement list is kept by 12/4 fp32 input-box handles");
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipMemcpy(out, h->qp_stats + 3 * h->max_batch + 18, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return MPCB_OK;

@@ -157,6 +157,12 @@ constexpr double AS_REF_U0 = 2.0;
 constexpr int AS_REF_PASSES = 10;
 // ... and converged instances whose set fixes at least this fraction of the input components
 constexpr int AS_REF_FIX_NUM = 3, AS_REF_FIX_DEN = 10;
+// The refinement kernel's own pass budget: refined passes per listed instance, counted from the
+// listed pass count and independent of max_as_iter (under the active set's cap a listed instance
+// had the cap minus its listed count, 47 at most at the default).  Out of budget the instance
+// keeps the outputs and the status of the kernel that listed it: the refinement never turns an OK
+// into MAXITER.
+constexpr int AS_REF_BUDGET = AS_IPM_AFTER;
 
 template <class T>
 struct SplitArgs {

@@ -269,3 +269,34 @@ def test_box_interior_point_from_start_matches_oracle():
     assert o['fallback'].sum() > B // 2
     assert (st == 0).all() and (o['status'] == 0).all()
     assert e < 1e-9
+
+
+def test_box_interior_point_from_start_matches_oracle_fp32():
+    """max_as_iter = 1 in fp32: the interior point from the start, then the refinement kernel on
+    each hand-over's set, with a pass budget of its own (mpcb_kernels.h AS_REF_BUDGET: under
+    max_as_iter it had one refined pass, and ended as MAXITER when that pass changed the set).
+    Every status OK, U inside the box to 2e-4, every instance that fp32 data can pin
+    (oracle.ocp.fp32_sensitivity <= 1e-5: all but 17 of this draw's 192) within 5e-5 normwise,
+    every instance within 1e-5 of the QP's optimal objective."""
+    from mpc_blaster_amd import BatchedMPC, MPCConfig
+    from oracle.ocp import fp32_sensitivity
+    from test_gpu_fuzz import qp_objective
+    from test_oracle_ocp import hard_box_inputs
+    N, B = 18, 192
+    inp = hard_box_inputs(B, N, 12)
+    x0, xref, uref, wind = (inp[k].astype(np.float32).astype(np.float64) for k in ('x0', 'xref', 'uref', 'wind'))
+    m = BatchedMPC(MPCConfig(N=N, dtype='f32', lbu=np.zeros(4), ubu=np.full(4, 65.0), max_as_iter=1), max_batch=B)
+    m.solve(x0, xref, uref, wind=wind)
+    u0, X, U, st = _outputs(m)
+    spec = OcpSpec(N=N, lbu=np.zeros(4), ubu=np.full(4, 65.0), max_as_iter=1)
+    o = mpc_solve(x0, xref, uref, spec, wind=wind, return_lin=True)
+    ill = fp32_sensitivity(o, x0, xref, uref, spec) > 1e-5
+    e = np.maximum(np.maximum(relerr(u0, o['u0']), relerr(X, o['X'])), relerr(U, o['U']))
+    gap = qp_objective(o, U, x0, xref, uref, spec) / np.abs(qp_objective(o, o['U'], x0, xref, uref, spec)) - 1.0
+    print(f'fp32 interior point from the start: {o["fallback"].sum()} of {B} handed over, status '
+          f'{np.bincount(st, minlength=5).tolist()}, {int(ill.sum())} fp32-ill-conditioned, the others max rel err '
+          f'{e[~ill].max():.2e}, objective gap max {gap.max():.2e}')
+    assert o['fallback'].sum() > B // 2 and ill.sum() <= 17
+    assert (st == 0).all() and (o['status'] == 0).all()
+    assert (U >= -2e-4).all() and (U <= 65 + 2e-4).all()
+    assert e[~ill].max() < 5e-5 and (gap < 1e-5).all()
