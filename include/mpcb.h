@@ -584,6 +584,58 @@ int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B,
                       void* hip_stream);
 
 /*
+ * mpcb_sim_step on the 17/6 model with the plant's parameters as an argument: x_out[b] =
+ * Phi(x[b], u[b]; p_b), one RK4 step of f17.  The plant's truth given apart from the controller's
+ * belief (mpcb_set_params): the 17/6 counterpart of `model` in mpcb_sim_step_pm.
+ *   params, params_sb   DEVICE array [B|1, 25] of the handle's dtype in the vector layout of
+ *             mpcb_set_params; instance b's vector starts at params + b * params_sb (elements).
+ *             params_sb == 0 broadcasts one vector; params_sb >= 25 is allowed and the pad elements
+ *             are never read; element alignment only.  NULL = mpcb_sim_step itself: the handle's
+ *             mpcb_set_params array at stage 0 with its stride and its count check, or the defaults.
+ *   every other argument: as for mpcb_sim_step (without the wind, a 12/4 extension)
+ * The kernel of mpcb_sim_step with the caller's pointer: the bits of mpcb_set_params(those rows)
+ * followed by mpcb_sim_step.  MPCB_E_UNSUPPORTED on a 12/4 handle.  MPCB_E_INVALID: as for
+ * mpcb_sim_step, and a parameter stride that is negative or between 1 and 24.
+ */
+int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const void* u,
+                      const void* params, int64_t params_sb, double T, void* x_out, void* hip_stream);
+
+/*
+ * Reverse mode of the 17/6 plant step (both dtypes).  With x_out = Phi(x, u; p) the step of
+ * mpcb_sim_step_p17 and gxn [B,17] the cotangent of x_out:
+ *   gx      [B,17] = (d x_out / d x)^T gxn
+ *   gu      [B,6]  = (d x_out / d u)^T gxn
+ *   gparams [B,25] = (d x_out / d p)^T gxn, in the parameter vector's own column-major order
+ *                    (mpcb_set_params); entry 24 is d/d T_blast
+ * One sweep back through the four RK4 stages: the exact derivative of the discrete RK4 map, not of
+ * the ODE.
+ *   x, u, params, params_sb, T   by the rules of mpcb_sim_step_p17
+ *   gxn       required
+ *   gx, gu, gparams   any may be NULL (not computed), but not all three; contiguous rows, element
+ *             alignment only.  gx may alias gxn (each instance's inputs are read before its outputs
+ *             are written); no other aliasing is allowed.
+ * Broadcast params (params_sb == 0, or NULL with a broadcast mpcb_set_params array or the defaults)
+ * still gives per-instance gparams rows; the caller sums them (the convention of gQ and gmodel).
+ * No gradient is given with respect to mass, J, the arms, gravity or T: those are the handle's.
+ * There is no status: an instance with a non-finite entry in x, u, gxn or its parameter vector gets
+ * NaN in every requested output row; the other instances keep their bits.  No atomics: the same
+ * call returns the same bits.
+ * MPCB_E_UNSUPPORTED on a 12/4 handle (mpcb_sim_step_vjp is its counterpart, and keeps refusing a
+ * 17/6 handle).  MPCB_E_INVALID: B > max_batch, a missing x, u or gxn, all three outputs NULL, a
+ * parameter stride that is negative or between 1 and 24, T <= 0, params == NULL with a non-broadcast
+ * mpcb_set_params array shorter than B.  A refused call writes nothing.
+ * Out of scope: weight gradients through a 17/6 closed loop (the weights are installed on the
+ * handle); stage-varying plant parameters (the plant step has one stage); gradients with respect to
+ * the controller's mpcb_set_params; the state box; rollout mode.
+ */
+int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B,
+                        const void* x, const void* u,
+                        const void* params, int64_t params_sb,
+                        double T, const void* gxn,
+                        void* gx, void* gu, void* gparams,
+                        void* hip_stream);
+
+/*
  * Synthetic inputs (SURVEY §8 d): Philox4x32-10 keyed by (seed, id_offset + i).
  *   ref_kind 0 = hover reference, 1 = per-instance sinusoid (c3);  wind may be NULL.
  * Writes x0 [B,nx], xref [B,N+1,nx] (or [1,...] if ref_kind==0 and xref_sb==0), uref likewise.

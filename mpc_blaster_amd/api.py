@@ -696,16 +696,47 @@ class BatchedMPC:
         self._keep = (xb, ub, wd)
         return A, Bm, xn
 
-    def sim_step(self, x, u, T=None, wind=None, model=None):
+    def _params_arg(self, params, B):
+        """A ``params=`` argument of the 17/6 plant step as (device tensor, stride): parameter vectors
+        [25] or [B|1, 25] in the layout of ``set_params``; wider rows are padding that the library
+        never reads."""
+        torch = _torch()
+        if self.nx != 17:
+            raise ValueError('params covers the 17/6 model only (12/4: model)')
+        if isinstance(params, np.ndarray) and not params.flags.writeable:
+            params = params.copy()   # torch.as_tensor warns on read-only arrays
+        t = torch.as_tensor(params, dtype=self.dtype, device=self._tdev)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2 or t.shape[1] < 25:
+            raise ValueError(f'params: expected [25] or [B|1, 25] (or wider, padded rows), got {tuple(t.shape)}')
+        if t.shape[0] != B and t.shape[0] != 1:
+            raise ValueError(f'params: batch {t.shape[0]} != {B}')
+        t = t.contiguous()
+        return t, 0 if t.shape[0] == 1 else t.shape[1]
+
+    def sim_step(self, x, u, T=None, wind=None, model=None, params=None):
         """Plant integrator: one RK4 step of length T (default dt) — AcadosSimSolver.solve().
         ``model``: a vehicle per instance (mpcb_sim_step_pm; 12/4 model), records [B|1, 14] as
-        ``pack_model`` builds them; an instance with a non-finite record entry gets a NaN row."""
+        ``pack_model`` builds them; an instance with a non-finite record entry gets a NaN row.
+        ``params``: the plant's parameter vectors (mpcb_sim_step_p17; 17/6 model), [25] or
+        [B|1, 25] in the layout of ``set_params``, which stays the controller's belief; a 12/4 handle
+        raises ``ValueError``."""
         torch = _torch()
         xs, _ = self._dev(x, (self.nx,), 'x')
         B = xs.shape[0]
         us, _ = self._dev(u, (self.nu,), 'u', B)
         wd, wd_sb = (None, 0) if wind is None else self._dev(wind, (3,), 'wind', B, allow_broadcast=True)
         xo = torch.empty_like(xs)
+        if params is not None:
+            pd, p_sb = self._params_arg(params, B)
+            if wind is not None or model is not None:
+                raise ValueError('wind and model are 12/4-model arguments: not together with params')
+            _lib.check(self.lib.mpcb_sim_step_p17(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(pd), p_sb,
+                                                  float(self.cfg.dt if T is None else T), self._ptr(xo),
+                                                  self._stream()))
+            self._keep = (xs, us, pd)
+            return xo
         if model is not None:
             md, m_sb = self._model_arg(model, B)
             _lib.check(self.lib.mpcb_sim_step_pm(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(wd), wd_sb,
@@ -749,6 +780,41 @@ class BatchedMPC:
                                               self._stream()))
         self._keep = (xs, us, gn, wd, md)
         return out
+
+    def sim_step_vjp17(self, x, u, gxn, T=None, params=None, want=('gx', 'gu')):
+        """Reverse mode of ``sim_step`` on the 17/6 model (mpcb_sim_step_vjp17): with ``gxn`` [B,17]
+        the cotangent of the step's output, a dict of device tensors with the keys of ``want``, any
+        non-empty subset of ``gx`` [B,17], ``gu`` [B,6], ``gparams`` [B,25] (the parameter vector's
+        own order; entry 24 is d/d T_blast).  ``T`` and ``params`` as for ``sim_step``; a broadcast
+        ``params`` still gives rows per instance, which the caller sums.  Without ``params``,
+        ``gparams`` is the gradient at the handle's ``set_params`` rows (stage 0) or the defaults.
+        An instance with a non-finite input gets NaN rows.  A 12/4 handle raises ``ValueError``."""
+        torch = _torch()
+        if self.nx != 17:
+            raise ValueError('sim_step_vjp17 covers the 17/6 model only (12/4: sim_step_vjp)')
+        cols = dict(gx=self.nx, gu=self.nu, gparams=25)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or len(set(want)) != len(want) or set(want) - set(cols):
+            raise ValueError(f'want: a non-empty subset of {tuple(cols)}, got {want}')
+        xs, _ = self._dev(x, (self.nx,), 'x')
+        B = xs.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        us, _ = self._dev(u, (self.nu,), 'u', B)
+        gn, _ = self._dev(gxn, (self.nx,), 'gxn', B)
+        pd, p_sb = (None, 0) if params is None else self._params_arg(params, B)
+        out = {k: torch.empty((B, cols[k]), dtype=self.dtype, device=self._tdev) for k in want}
+        _lib.check(self.lib.mpcb_sim_step_vjp17(self._h, B, self._ptr(xs), self._ptr(us), self._ptr(pd), p_sb,
+                                                float(self.cfg.dt if T is None else T), self._ptr(gn),
+                                                *(self._ptr(out.get(k)) for k in cols), self._stream()))
+        self._keep = (xs, us, gn, pd)
+        return out
+
+    def sim_step_diff17(self, x, u, T=None, params=None):
+        """``sim_step`` on the 17/6 model as a differentiable torch operation: gradients flow to the
+        tensors ``x``, ``u`` and ``params`` (see ``mpc_blaster_amd.autograd.sim_step_diff17``)."""
+        from .autograd import sim_step_diff17
+        return sim_step_diff17(self, x, u, T=T, params=params)
 
     def sim_step_diff(self, x, u, T=None, wind=None, model=None):
         """``sim_step`` as a differentiable torch operation: gradients flow to the tensors ``x``,

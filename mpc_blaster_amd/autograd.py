@@ -68,6 +68,16 @@ between forward and backward raises ``RuntimeError`` (above); with a record it g
 model only (a 17/6 handle raises ``ValueError``); not differentiable
 twice.
 
+The 17/6 plant step.  ``sim_step_diff17(mpc, x, u, T=None, params=None) -> x_out`` runs
+``BatchedMPC.sim_step(params=)`` in the forward pass and one ``mpcb_sim_step_vjp17`` call in the
+backward pass, which requests exactly the outputs whose inputs need a gradient: ``x``, ``u`` and
+``params`` (the plant's 25-vectors in the layout of ``set_params``; entry 24 is T_blast).  A
+``[25]`` or ``[1, 25]`` tensor receives the sum over the batch, in its own shape and dtype; rows wider
+than 25 get zeros in the pad columns.  Mass, J, the arms, gravity and ``T`` carry no gradient: they
+are the handle's.  Without ``params`` the step reads the handle's ``set_params`` rows, so
+``set_params`` or ``set_t_blast`` between forward and backward raises ``RuntimeError`` (above); with a
+``params`` tensor it goes through.  A 12/4 handle raises ``ValueError``.
+
 torch is imported on first use, as in ``api.py``.
 """
 from __future__ import annotations
@@ -271,6 +281,74 @@ def _sim_function():
 
     _SIM = SimStep
     return _SIM
+
+
+_SIM17 = None
+
+
+def _sim17_function():
+    global _SIM17
+    if _SIM17 is not None:
+        return _SIM17
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SimStep17(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, mpc, x, u, T, params):
+            if mpc.nx != 17:
+                raise ValueError('sim_step_diff17 covers the 17/6 model only (12/4: sim_step_diff)')
+            xs, _ = mpc._dev(x.detach(), (mpc.nx,), 'x')
+            B = xs.shape[0]
+            us, _ = mpc._dev(u.detach(), (mpc.nu,), 'u', B)
+            pd = None
+            if params is not None:
+                pd, _ = mpc._params_arg(params.detach() if torch.is_tensor(params) else params, B)
+            xo = mpc.sim_step(xs, us, T=T, params=pd)
+            ctx.mpc, ctx.T = mpc, T
+            ctx.mversion = mpc._model_version   # read again by the backward pass unless params is given
+            ctx.has = pd is not None
+            ctx.meta = [(tuple(t.shape), t.dtype) if torch.is_tensor(t) else None for t in (x, u, params)]
+            ctx.save_for_backward(xs, us, *((pd,) if pd is not None else ()))
+            return xo
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g):
+            mpc = ctx.mpc
+            xs, us = ctx.saved_tensors[:2]
+            pd = ctx.saved_tensors[2] if ctx.has else None
+            need = [ctx.needs_input_grad[i] for i in (1, 2, 4)]
+            keys = ('gx', 'gu', 'gparams')
+            want = tuple(k for k, n in zip(keys, need) if n)
+            grads = [None] * 3
+            if want:
+                if pd is None:
+                    _same_model(mpc, ctx.mversion)
+                out = mpc.sim_step_vjp17(xs, us, g.to(mpc.dtype), T=ctx.T, params=pd, want=want)
+                for i, k in enumerate(keys):
+                    if k not in out:
+                        continue
+                    shape, dt = ctx.meta[i]
+                    v = out[k]
+                    rows = 1 if len(shape) == 1 else shape[0]
+                    if rows == 1 and v.shape[0] != 1:
+                        v = v.sum(dim=0, keepdim=True)   # one row for the whole batch
+                    if k == 'gparams' and shape[-1] > v.shape[1]:
+                        v = torch.nn.functional.pad(v, (0, shape[-1] - v.shape[1]))   # pad columns: zeros
+                    grads[i] = v.reshape(shape).to(dt)
+            return (None, grads[0], grads[1], None, grads[2])
+
+    _SIM17 = SimStep17
+    return _SIM17
+
+
+def sim_step_diff17(mpc, x, u, T=None, params=None):
+    """x_out [B,17] of ``mpc.sim_step(params=)`` on the 17/6 model, differentiable with respect to the
+    torch tensors ``x``, ``u`` and ``params`` (module docstring)."""
+    import torch
+    x, u = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev) for t in (x, u))
+    return _sim17_function().apply(mpc, x, u, T, params)
 
 
 def sim_step_diff(mpc, x, u, T=None, wind=None, model=None):

@@ -9,7 +9,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['mpcb_solve.hip', 'mpcb_split.hip', 'mpcb_rollout.hip', 'mpcb_box.hip', 'mpcb_as.hip', 'mpcb_aux.hip', 'mpcb_full.hip', 'mpcb_r17.hip',
-           'mpcb_poc.hip', 'mpcb_eval.hip', 'mpcb_vjp.hip', 'mpcb_gains.hip', 'mpcb_pw.hip', 'mpcb_simvjp.hip', 'mpcb_capi.hip']
+           'mpcb_poc.hip', 'mpcb_eval.hip', 'mpcb_vjp.hip', 'mpcb_gains.hip', 'mpcb_pw.hip', 'mpcb_simvjp.hip', 'mpcb_simvjp17.hip',
+           'mpcb_capi.hip']
 OUT = os.path.join(HERE, 'libmpcblaster.so')
 ARCH = os.environ.get('MPCB_OFFLOAD_ARCH', 'gfx950')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

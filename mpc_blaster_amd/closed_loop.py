@@ -12,7 +12,7 @@ from .api import BatchedMPC
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
                 xbar=None, ubar=None, diagnostics=False, resolve_every: int = 1, feedback: bool = False,
-                active_tol=None, weights=None, model=None, plant_model=None):
+                active_tol=None, weights=None, model=None, plant_model=None, plant_params=None):
     """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
 
     ``resolve_every = h > 1`` (h <= N) models a controller slower than the plant: the solve runs
@@ -36,6 +36,11 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     goes to every solve and, with ``feedback=True``, to the gains.  ``plant_model`` is the truth:
     it goes to every plant step.  Either may be given alone; the other side then uses the handle's
     vehicle.  ``model`` not together with ``diagnostics``, which evaluates with the handle's model.
+
+    ``plant_params`` (17/6 model; a 12/4 handle raises ``ValueError``): the plant's parameter vectors
+    [25] or [B|1, 25] in the layout of ``set_params``.  They go to every plant step
+    (``sim_step(params=)``), with ``resolve_every`` / ``feedback`` too; the controller keeps the
+    handle's ``set_params``.  The parameter-mismatch Monte Carlo on one handle.
 
     ``diagnostics=True`` evaluates the new iterate after each solve (``BatchedMPC.evaluate`` with
     that step's x0) and returns a fourth value: a dict of [B, nsim] tensors ``cost``, ``res_eq``,
@@ -64,6 +69,9 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
             mkw = dict(model=mpc._model_arg(model, B0)[0])
         if plant_model is not None:
             pkw = dict(model=mpc._model_arg(plant_model, B0)[0])
+    if plant_params is not None:
+        B0 = x0.shape[0] if hasattr(x0, 'shape') else len(x0)
+        pkw = dict(params=mpc._params_arg(plant_params, B0)[0])   # ValueError on a 12/4 handle
     if h < 1 or h > mpc.cfg.N:
         raise ValueError(f'resolve_every = {resolve_every}: expected 1 <= resolve_every <= N = {mpc.cfg.N}')
     if h > 1 or feedback:
@@ -159,10 +167,11 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
 
 
 def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, wind=None, plant_T=None,
-                     weights=None, plant_model=None, warm_start=True):
-    """The loop of ``closed_loop`` as a differentiable torch operation (12/4 model): returns
-    (X_sim [B, nsim+1, 12], U_sim [B, nsim, 4], status [B] = max over steps).  Each step is
-    ``solve_iterate_diff`` followed by ``sim_step_diff`` (``mpc_blaster_amd.autograd``), so a loss on
+                     weights=None, plant_model=None, warm_start=True, plant_params=None, active_tol=None):
+    """The loop of ``closed_loop`` as a differentiable torch operation: returns
+    (X_sim [B, nsim+1, 12], U_sim [B, nsim, 4], status [B] = max over steps; 17 and 6 on the full
+    model).  Each step is ``solve_iterate_diff`` followed by ``sim_step_diff`` (``sim_step_diff17`` on
+    the 17/6 model; ``mpc_blaster_amd.autograd``), so a loss on
     X_sim, U_sim can be differentiated with respect to the torch tensors ``x0``, ``x_ref``, ``u_ref``,
     the tensors in ``weights`` and ``plant_model``.  The forward values are ``closed_loop``'s with
     the same arguments: the same entry points in the same order.
@@ -179,11 +188,31 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     path through the iterate.  ``warm_start=False``: every step linearises at the given
     (``xbar``, ``ubar``); the loop is then piecewise smooth in the differentiated inputs and the
     gradient is exact on the active sets of the forward pass.  An instance whose solve reports a
-    status other than 0 at some step passes no gradient through that solve."""
+    status other than 0 at some step passes no gradient through that solve.
+
+    The 17/6 model.  The loop chains ``solve_iterate_diff`` with ``sim_step_diff17`` and is
+    differentiable in ``x0``, ``x_ref``, ``u_ref`` and ``plant_params`` (the plant's parameter vectors
+    [25] or [B|1, 25], ``closed_loop``'s argument; a one-row tensor receives the batch sum).
+    ``active_tol`` is ``solve_iterate_diff``'s active-set tolerance.  The controller's parameters are
+    the handle's ``set_params`` and constants.  Refused with ``ValueError``: ``weights`` (on 17/6 they
+    are installed on the handle, so every forward pass would invalidate the previous step's
+    backward), ``plant_model``, ``wind``, and a handle with the state box.  On a 12/4 handle
+    ``plant_params`` and ``active_tol`` are refused."""
     import torch
-    from .autograd import sim_step_diff, solve_iterate_diff
-    if mpc.nx == 17:
-        raise ValueError('closed_loop_diff covers the 12/4 model only')
+    from .autograd import sim_step_diff, sim_step_diff17, solve_iterate_diff
+    full = mpc.nx == 17
+    if full:
+        if weights is not None:
+            raise ValueError('closed_loop_diff on the 17/6 model takes no weights: they are installed on the '
+                             'handle, and every forward pass would invalidate the previous step\'s backward')
+        if plant_model is not None:
+            raise ValueError('plant_model covers the 12/4 model only (17/6: plant_params)')
+        if wind is not None:
+            raise ValueError('wind is a 12/4-model extension')
+        if mpc.cfg.lbx is not None:
+            raise ValueError('closed_loop_diff does not cover the 17/6 state box (solve_iterate_diff)')
+    elif plant_params is not None or active_tol is not None:
+        raise ValueError('plant_params and active_tol belong to the 17/6 model')
     wkw = {}
     if weights is not None:
         unknown = set(weights) - {'Q', 'R', 'QN'}
@@ -197,12 +226,18 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     worst = torch.zeros((x.shape[0],), dtype=torch.int32, device=dev)
     Xs, Us = [x], []
     for _ in range(nsim):
-        u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, wind=wind, per_instance_weights=bool(wkw),
-                                      **wkw)
+        if full:
+            u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol)
+        else:
+            u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, wind=wind, per_instance_weights=bool(wkw),
+                                          **wkw)
         worst = torch.maximum(worst, mpc.get_status())
         if warm_start:
             xb, ub = X.detach(), U.detach()
-        x = sim_step_diff(mpc, x, u0, T=plant_T, wind=wind, model=plant_model)
+        if full:
+            x = sim_step_diff17(mpc, x, u0, T=plant_T, params=plant_params)
+        else:
+            x = sim_step_diff(mpc, x, u0, T=plant_T, wind=wind, model=plant_model)
         Xs.append(x)
         Us.append(u0)
     return torch.stack(Xs, dim=1), torch.stack(Us, dim=1), worst

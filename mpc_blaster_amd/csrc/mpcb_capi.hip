@@ -1441,6 +1441,74 @@ extern "C" int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B, const void* x, const
   return MPCB_OK;
 }
 
+static int check_params_stride(int64_t params_sb) {
+  if (params_sb < 0 || (params_sb > 0 && params_sb < NP17))
+    return fail(MPCB_E_INVALID, "parameter stride %lld: 0 (broadcast) or >= %d", (long long)params_sb, NP17);
+  return MPCB_OK;
+}
+
+// The parameter vectors a 17/6 plant step reads when the caller passes none: the handle's
+// mpcb_set_params array at stage 0 with its stride, or the defaults in the weights block.
+template <class T>
+static const T* plant_params(const mpcb_handle* h, int64_t* sb) {
+  *sb = h->params ? h->params_sb : 0;
+  return h->params ? (const T*)h->params : reinterpret_cast<const Weights17<T>*>(h->weights)->p;
+}
+
+extern "C" int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* params,
+                                 int64_t params_sb, double T, void* x_out, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_sim_step_p17 covers the 17/6 model only (12/4: mpcb_sim_step_pm)");
+  if (int rc = check_params_stride(params_sb)) return rc;
+  if (!params) return mpcb_sim_step(h, B, x, u, nullptr, 0, T, x_out, stream);
+  if (B < 0) return fail(MPCB_E_INVALID, "negative batch");
+  if (B == 0) return MPCB_OK;
+  if (!x || !u || !x_out) return fail(MPCB_E_INVALID, "null array");
+  if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
+  HIP_TRY(hipSetDevice(h->device));
+  hipError_t e;
+  if (h->cfg.dtype == MPCB_F64)
+    e = launch_sim_step17<double>(B, T, h->Md, (const double*)params, params_sb, (const double*)x,
+                                  (const double*)u, (double*)x_out, (hipStream_t)stream);
+  else
+    e = launch_sim_step17<float>(B, (float)T, h->Mf, (const float*)params, params_sb, (const float*)x,
+                                 (const float*)u, (float*)x_out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_p17 launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* params,
+                                   int64_t params_sb, double T, const void* gxn, void* gx, void* gu,
+                                   void* gparams, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_sim_step_vjp17 covers the 17/6 model only (12/4: mpcb_sim_step_vjp)");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_params_stride(params_sb)) return rc;
+  if (!gx && !gu && !gparams) return fail(MPCB_E_INVALID, "no output requested");
+  if (B == 0) return MPCB_OK;
+  if (!x || !u || !gxn) return fail(MPCB_E_INVALID, "null array");
+  if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
+  if (!params) {
+    if (int rc = check_params(h, B)) return rc;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  hipError_t e;
+  if (h->cfg.dtype == MPCB_F64) {
+    const double* p = params ? (const double*)params : plant_params<double>(h, &params_sb);
+    e = launch_sim_step_vjp17<double>(B, T, h->Md, p, params_sb, (const double*)x, (const double*)u,
+                                      (const double*)gxn, (double*)gx, (double*)gu, (double*)gparams,
+                                      (hipStream_t)stream);
+  } else {
+    const float* p = params ? (const float*)params : plant_params<float>(h, &params_sb);
+    e = launch_sim_step_vjp17<float>(B, (float)T, h->Mf, p, params_sb, (const float*)x, (const float*)u,
+                                     (const float*)gxn, (float*)gx, (float*)gu, (float*)gparams,
+                                     (hipStream_t)stream);
+  }
+  if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_vjp17 launch: %s", hipGetErrorString(e));
+  return MPCB_OK;
+}
+
 extern "C" int mpcb_gen_inputs(mpcb_handle* h, int64_t B, uint64_t seed, uint64_t id_offset, int ref_kind, void* x0,
                     void* xref, int64_t xref_sb, void* uref, int64_t uref_sb, void* wind, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");

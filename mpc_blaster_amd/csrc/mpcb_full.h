@@ -195,6 +195,206 @@ __device__ __forceinline__ void rk4_17(const T* __restrict__ x, const T* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reverse mode of rk4_17 (mpcb_sim_step_vjp17): the 17/6 counterpart of f_nom_lin / f_adj_lin /
+// rk4_adj in mpcb_model.h.  The nominal pass captures F17_LIN_N scalars per RK4 stage, the sweep
+// applies the transpose of f17_tan's TAN branch from them: no transcendental, no division.
+// ---------------------------------------------------------------------------------------------
+constexpr int F17_LIN_N = 15;      // captured scalars per RK4 stage
+constexpr int F17_LIN_STAGE = 60;  // per step (4 stages)
+
+// f17 (the expressions of f17_tan) and the stage's captured scalars
+//   c = [sf cf st ct sp cp s1 c1 s2 c2 | ict A | wx wy wz],  A = sf wy + cf wz.
+// What else the sweep needs (tt, R, the body force, J w) it recomputes from these by products.
+template <class T>
+__device__ __forceinline__ void f17_nom_lin(const T* __restrict__ x, const T* __restrict__ u,
+                                            const Model<T>& M, const P17<T>& P, T* __restrict__ f,
+                                            T* __restrict__ c) {
+  T tsn[5], tcs[5];
+  Trig17Serial()(x, tsn, tcs);
+  const T sf = tsn[0], cf = tcs[0], st = tsn[1], ct = tcs[1], sp = tsn[2], cp = tcs[2];
+  const T s1 = tsn[3], c1 = tcs[3], s2 = tsn[4], c2 = tcs[4];
+  const T ict = recip(ct);
+  const T tt = st * ict;
+  const T wx = x[9], wy = x[10], wz = x[11];
+  f[0] = x[6]; f[1] = x[7]; f[2] = x[8];
+  const T a = sf * wy + cf * wz;
+  const T b = cf * wy - sf * wz;
+  const T ed0 = wx + tt * a, ed1 = b, ed2 = a * ict;
+  f[3] = ed0; f[4] = ed1; f[5] = ed2;
+  const T cpst = cp * st, spst = sp * st;
+  const T R00 = cp * ct, R01 = cpst * sf - sp * cf, R02 = cpst * cf + sp * sf;
+  const T R10 = sp * ct, R11 = spst * sf + cp * cf, R12 = spst * cf - cp * sf;
+  const T R20 = -st, R21 = ct * sf, R22 = ct * cf;
+  const T Tsum = (u[0] + u[1]) + (u[2] + u[3]);
+  const T fb0 = P.tb * (s1 * c2), fb1 = -P.tb * s2, fb2 = Tsum + P.tb * (c1 * c2);
+  f[6] = (R00 * fb0 + R01 * fb1 + R02 * fb2) * M.minv;
+  f[7] = (R10 * fb0 + R11 * fb1 + R12 * fb2) * M.minv;
+  f[8] = (R20 * fb0 + R21 * fb1 + R22 * fb2) * M.minv - M.g;
+  const T jw0 = M.J[0] * wx + M.J[1] * wy + M.J[2] * wz;
+  const T jw1 = M.J[3] * wx + M.J[4] * wy + M.J[5] * wz;
+  const T jw2 = M.J[6] * wx + M.J[7] * wy + M.J[8] * wz;
+  const T m0 = (u[1] + u[3] - u[0] - u[2]) * M.ly - (wy * jw2 - wz * jw1);
+  const T m1 = (u[1] + u[2] - u[0] - u[3]) * M.lx - (wz * jw0 - wx * jw2);
+  const T m2 = (u[2] + u[3] - u[0] - u[1]) * M.c - (wx * jw1 - wy * jw0);
+  f[9] = M.Jinv[0] * m0 + M.Jinv[1] * m1 + M.Jinv[2] * m2;
+  f[10] = M.Jinv[3] * m0 + M.Jinv[4] * m1 + M.Jinv[5] * m2;
+  f[11] = M.Jinv[6] * m0 + M.Jinv[7] * m1 + M.Jinv[8] * m2;
+  f[12] = u[4];
+  f[13] = u[5];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    f[14 + i] = P.Jp[i * 3] * x[6] + P.Jp[i * 3 + 1] * x[7] + P.Jp[i * 3 + 2] * x[8] +
+                P.Je[i * 3] * ed0 + P.Je[i * 3 + 1] * ed1 + P.Je[i * 3 + 2] * ed2 +
+                P.Ja[i * 2] * u[4] + P.Ja[i * 2 + 1] * u[5];
+  c[0] = sf; c[1] = cf; c[2] = st; c[3] = ct; c[4] = sp; c[5] = cp;
+  c[6] = s1; c[7] = c1; c[8] = s2; c[9] = c2; c[10] = ict; c[11] = a;
+  c[12] = wx; c[13] = wy; c[14] = wz;
+}
+
+// px += (df/dx)^T a, pu += (df/du)^T a and, with WP, gtb += (df/dT_blast)^T a at the stage whose
+// scalars are c: the transpose of f17_tan's TAN branch.  Relative to f_adj_lin (mpcb_model.h):
+//  * the POC rows q = a[14..16] reach v (J_p^T q), the Euler rates (J_e^T q joins their adjoint
+//    before the Euler-rate block) and the swivel rates (J_a^T q);
+//  * v_dot = minv R fb with the full rotation and fb = (tb s1 c2, -tb s2, Tsum + tb c1 c2):
+//    gfb = minv R^T a[6..8] feeds the swivel angles, the motors and T_blast, gR = minv a[6..8] fb^T
+//    the six attitude trig adjoints.
+// Nothing reads the POC states, so px[14..16] is left alone.  The 24 Jacobian entries of the
+// parameter gradient have a closed form outside the sweep (rk4_17_adj).
+template <class T, bool WP>
+__device__ __forceinline__ void f17_adj_lin(const T* __restrict__ c, const T* __restrict__ u,
+                                            const Model<T>& M, const P17<T>& P, const T* __restrict__ a,
+                                            T* __restrict__ px, T* __restrict__ pu, T& gtb) {
+  const T sf = c[0], cf = c[1], st = c[2], ct = c[3], sp = c[4], cp = c[5];
+  const T s1 = c[6], c1 = c[7], s2 = c[8], c2 = c[9], ict = c[10], av = c[11];
+  const T wx = c[12], wy = c[13], wz = c[14];
+  const T tt = st * ict;
+  const T q0 = a[14], q1 = a[15], q2 = a[16];
+  // ---- p_dot = v, and J_p v in the POC rows
+  px[6] += a[0] + (P.Jp[0] * q0 + P.Jp[3] * q1 + P.Jp[6] * q2);
+  px[7] += a[1] + (P.Jp[1] * q0 + P.Jp[4] * q1 + P.Jp[7] * q2);
+  px[8] += a[2] + (P.Jp[2] * q0 + P.Jp[5] * q1 + P.Jp[8] * q2);
+  // ---- alpha_dot = u[4..5], and J_a alpha_dot in the POC rows
+  pu[4] += a[12] + (P.Ja[0] * q0 + P.Ja[2] * q1 + P.Ja[4] * q2);
+  pu[5] += a[13] + (P.Ja[1] * q0 + P.Ja[3] * q1 + P.Ja[5] * q2);
+  // ---- eta_dot: ed0 = wx + tt A, ed1 = b, ed2 = A ict, read by f[3..5] and by J_e eta_dot
+  const T e0 = a[3] + (P.Je[0] * q0 + P.Je[3] * q1 + P.Je[6] * q2);
+  const T e1 = a[4] + (P.Je[1] * q0 + P.Je[4] * q1 + P.Je[7] * q2);
+  const T e2 = a[5] + (P.Je[2] * q0 + P.Je[5] * q1 + P.Je[8] * q2);
+  const T gA = tt * e0 + ict * e2;
+  const T gtt = av * e0;
+  const T gict = av * e2 + st * gtt;
+  T gst = ict * gtt;
+  T gct = -(ict * ict) * gict;
+  T gsf = wy * gA - wz * e1;
+  T gcf = wz * gA + wy * e1;
+  T gwx = e0;
+  T gwy = sf * gA + cf * e1;
+  T gwz = cf * gA - sf * e1;
+  // ---- v_dot = minv R fb - g e3
+  const T cpst = cp * st, spst = sp * st;
+  const T R00 = cp * ct, R01 = cpst * sf - sp * cf, R02 = cpst * cf + sp * sf;
+  const T R10 = sp * ct, R11 = spst * sf + cp * cf, R12 = spst * cf - cp * sf;
+  const T R20 = -st, R21 = ct * sf, R22 = ct * cf;
+  const T Tsum = (u[0] + u[1]) + (u[2] + u[3]);
+  const T s1c2 = s1 * c2, c1c2 = c1 * c2;
+  const T fb0 = P.tb * s1c2, fb1 = -P.tb * s2, fb2 = Tsum + P.tb * c1c2;
+  const T v0 = M.minv * a[6], v1 = M.minv * a[7], v2 = M.minv * a[8];
+  const T gfb0 = R00 * v0 + R10 * v1 + R20 * v2;
+  const T gfb1 = R01 * v0 + R11 * v1 + R21 * v2;
+  const T gfb2 = R02 * v0 + R12 * v1 + R22 * v2;
+  // gR[r][c] = v_r fb_c into the trig adjoints
+  const T g01 = v0 * fb1, g02 = v0 * fb2, g11 = v1 * fb1, g12 = v1 * fb2;
+  const T gcpst = sf * g01 + cf * g02;
+  const T gspst = sf * g11 + cf * g12;
+  T gcp = ct * (v0 * fb0) + cf * g11 - sf * g12 + st * gcpst;
+  T gsp = ct * (v1 * fb0) - cf * g01 + sf * g02 + st * gspst;
+  gct += cp * (v0 * fb0) + sp * (v1 * fb0) + sf * (v2 * fb1) + cf * (v2 * fb2);
+  gst += cp * gcpst + sp * gspst - v2 * fb0;
+  gsf += cpst * g01 + sp * g02 + spst * g11 - cp * g12 + ct * (v2 * fb1);
+  gcf += cpst * g02 - sp * g01 + cp * g11 + spst * g12 + ct * (v2 * fb2);
+  px[3] += cf * gsf - sf * gcf;
+  px[4] += ct * gst - st * gct;
+  px[5] += cp * gsp - sp * gcp;
+  // the swivelled thrust: fb = (tb s1 c2, -tb s2, Tsum + tb c1 c2)
+  const T gs1 = P.tb * c2 * gfb0, gc1 = P.tb * c2 * gfb2;
+  const T gs2 = -P.tb * gfb1, gc2 = P.tb * (s1 * gfb0 + c1 * gfb2);
+  px[12] += c1 * gs1 - s1 * gc1;
+  px[13] += c2 * gs2 - s2 * gc2;
+  if constexpr (WP) gtb += s1c2 * gfb0 - s2 * gfb1 + c1c2 * gfb2;
+  // ---- omega_dot = Jinv m,  m = Mom(u) - w x J w
+  const T gm0 = M.Jinv[0] * a[9] + M.Jinv[3] * a[10] + M.Jinv[6] * a[11];
+  const T gm1 = M.Jinv[1] * a[9] + M.Jinv[4] * a[10] + M.Jinv[7] * a[11];
+  const T gm2 = M.Jinv[2] * a[9] + M.Jinv[5] * a[10] + M.Jinv[8] * a[11];
+  const T m0 = M.ly * gm0, m1 = M.lx * gm1, m2 = M.c * gm2;
+  pu[0] += gfb2 - m0 - m1 - m2;
+  pu[1] += gfb2 + m0 + m1 - m2;
+  pu[2] += gfb2 - m0 + m1 + m2;
+  pu[3] += gfb2 + m0 - m1 + m2;
+  const T jw0 = M.J[0] * wx + M.J[1] * wy + M.J[2] * wz;
+  const T jw1 = M.J[3] * wx + M.J[4] * wy + M.J[5] * wz;
+  const T jw2 = M.J[6] * wx + M.J[7] * wy + M.J[8] * wz;
+  gwx += jw2 * gm1 - jw1 * gm2;
+  gwy += jw0 * gm2 - jw2 * gm0;
+  gwz += jw1 * gm0 - jw0 * gm1;
+  const T gj0 = wy * gm2 - wz * gm1;
+  const T gj1 = wz * gm0 - wx * gm2;
+  const T gj2 = wx * gm1 - wy * gm0;
+  px[9] += gwx + M.J[0] * gj0 + M.J[3] * gj1 + M.J[6] * gj2;
+  px[10] += gwy + M.J[1] * gj0 + M.J[4] * gj1 + M.J[7] * gj2;
+  px[11] += gwz + M.J[2] * gj0 + M.J[5] * gj1 + M.J[8] * gj2;
+}
+
+// Nominal RK4 step of f17 that keeps every stage's captured scalars in C (F17_LIN_STAGE values,
+// stage-major) and returns the step's increment inc = x_out - x = h/6 (k1 + 2 k2 + 2 k3 + k4),
+// formed without the subtraction.
+template <class T>
+__device__ __forceinline__ void rk4_17_nom(const T* __restrict__ x, const T* __restrict__ u, T h,
+                                           const Model<T>& M, const P17<T>& P, T* __restrict__ inc,
+                                           T* __restrict__ C) {
+  T k[NX17], xs[NX17];
+  const T h2 = T(0.5) * h, h6 = h / T(6);
+  f17_nom_lin<T>(x, u, M, P, k, C);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { inc[i] = k[i]; xs[i] = x[i] + h2 * k[i]; }
+  f17_nom_lin<T>(xs, u, M, P, k, C + F17_LIN_N);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { inc[i] += T(2) * k[i]; xs[i] = x[i] + h2 * k[i]; }
+  f17_nom_lin<T>(xs, u, M, P, k, C + 2 * F17_LIN_N);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { inc[i] += T(2) * k[i]; xs[i] = x[i] + h * k[i]; }
+  f17_nom_lin<T>(xs, u, M, P, k, C + 3 * F17_LIN_N);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) inc[i] = h6 * (inc[i] + k[i]);
+}
+
+// Reverse sweep of rk4_17_nom by the recurrence documented at rk4_adj (mpcb_model.h): lam is the
+// cotangent of x_out, gx = (dPhi/dx)^T lam, gu = (dPhi/du)^T lam, gtb = (dPhi/dT_blast)^T lam (WP).
+// px[14..16] stays 0 at every stage, so a[14 + i] is lam[14 + i] times the stage's RK4 weight.
+template <class T, bool WP>
+__device__ __forceinline__ void rk4_17_adj(const T* __restrict__ C, const T* __restrict__ u, T h,
+                                           const Model<T>& M, const P17<T>& P, const T* __restrict__ lam,
+                                           T* __restrict__ gx, T* __restrict__ gu, T& gtb) {
+  const T h2 = T(0.5) * h, h6 = h / T(6), h3 = h / T(3);
+  T a[NX17], p[NX17];
+#pragma unroll
+  for (int m = 0; m < NU17; ++m) gu[m] = T(0);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { gx[i] = lam[i]; a[i] = h6 * lam[i]; p[i] = T(0); }
+  f17_adj_lin<T, WP>(C + 3 * F17_LIN_N, u, M, P, a, p, gu, gtb);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { gx[i] += p[i]; a[i] = h3 * lam[i] + h * p[i]; p[i] = T(0); }
+  f17_adj_lin<T, WP>(C + 2 * F17_LIN_N, u, M, P, a, p, gu, gtb);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { gx[i] += p[i]; a[i] = h3 * lam[i] + h2 * p[i]; p[i] = T(0); }
+  f17_adj_lin<T, WP>(C + F17_LIN_N, u, M, P, a, p, gu, gtb);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) { gx[i] += p[i]; a[i] = h6 * lam[i] + h2 * p[i]; p[i] = T(0); }
+  f17_adj_lin<T, WP>(C, u, M, P, a, p, gu, gtb);
+#pragma unroll
+  for (int i = 0; i < NX17; ++i) gx[i] += p[i];
+}
+
 // DPP row broadcast (v_mov_b32_dpp row_newbcast): lane L of every 16-lane row hands v to the row.
 template <int L> __device__ __forceinline__ float rowbc(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x150 + L, 0xF, 0xF, true));
@@ -489,6 +689,11 @@ hipError_t launch_linearize17(int64_t B, int N, T h, const Model<T>& M, const T*
 template <class T>
 hipError_t launch_sim_step17(int64_t B, T h, const Model<T>& M, const T* p, int64_t p_sb,
                              const T* x, const T* u, T* xo, hipStream_t st);
+// mpcb_sim_step_vjp17 (mpcb_simvjp17.hip): the reverse sweep of that step.  p is never null (the
+// caller resolves the handle's array or the defaults); any output may be null.
+template <class T>
+hipError_t launch_sim_step_vjp17(int64_t B, T h, const Model<T>& M, const T* p, int64_t p_sb, const T* x,
+                                 const T* u, const T* gxn, T* gx, T* gu, T* gparams, hipStream_t st);
 template <class T> hipError_t launch_eval17(const EvalArgs<T>& a, hipStream_t st);   // mpcb_eval.hip
 
 }  // namespace mpcb
