@@ -64,6 +64,14 @@ LaunchLog& launch_log() {
 }
 }  // namespace mpcb
 
+// A slot workspace (one slot = one wavefront = GROUPS instances) of the 16-lanes-per-instance
+// kernels: allocated by the first call of its entry point (ensure_slots), not counted in
+// scratch_bytes; grid = its resident slots.
+struct SlotWs {
+  void* mem = nullptr;
+  int grid = 0;
+};
+
 struct mpcb_handle {
   mpcb_config cfg;
   const int32_t* as_order_dbg = nullptr;   // (MPCB_AS_ORDER_DBG builds) the active-set kernel's order
@@ -101,16 +109,71 @@ struct mpcb_handle {
   void* u_scratch = nullptr;     // fp32 12/4 input box: U when the caller passes none (the
                                  // refinement kernel restarts from the active set's U, mpcb_as.h)
   const void* last_fn[LOG_SLOTS] = {};   // kernels the last solve launched (mpcb_last_kernels)
-  void* vjp_scratch = nullptr;   // mpcb_solve_vjp's slot workspace: allocated by its first call, not
-                                 // counted in scratch_bytes
-  int vjp_grid = 0;              // ... and its resident slots
-  void* gains_scratch = nullptr; // mpcb_solve_gains' slot workspace (12/4): allocated by its first call,
-  int gains_grid = 0;            // ... its resident slots; the 17/6 model uses vjp17_scratch
+  SlotWs vjp_ws;                 // mpcb_solve_vjp (and _w, _pw)
+  SlotWs gains_ws;               // mpcb_solve_gains (12/4; the 17/6 model uses vjp17_scratch)
+  SlotWs pw_ws;                  // mpcb_solve_iterate_pw (and _pm)
   void* vjp17_scratch = nullptr; // mpcb_solve_vjp17's chunk workspace: allocated by its first call, not
                                  // counted in scratch_bytes
-  void* pw_scratch = nullptr;    // mpcb_solve_iterate_pw's slot workspace: allocated by its first call,
-  int pw_grid = 0;               // not counted in scratch_bytes; its resident slots
 };
+
+static int check_batch(const mpcb_handle* h, int64_t B) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (B < 0 || B > h->max_batch)
+    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  return MPCB_OK;
+}
+
+// f(Tag<double>{}) or f(Tag<float>{}) by the handle's dtype: `using T = typename decltype(t)::type`
+template <class T> struct Tag { using type = T; };
+template <class F>
+static auto by_dtype(const mpcb_handle* h, F&& f) {
+  return h->cfg.dtype == MPCB_F64 ? f(Tag<double>{}) : f(Tag<float>{});
+}
+
+template <class T>
+static const Model<T>& model_of(const mpcb_handle* h) {
+  if constexpr (sizeof(T) == 8) return h->Md; else return h->Mf;
+}
+
+// The parameter vectors a 17/6 call reads when the caller passes none: the handle's mpcb_set_params
+// array with its strides, or the defaults in the weights block (strides 0).
+template <class T>
+static const T* params17(const mpcb_handle* h, int64_t* sb, int64_t* kb = nullptr) {
+  *sb = h->params ? h->params_sb : 0;
+  if (kb) *kb = h->params ? h->params_kb : 0;
+  return h->params ? (const T*)h->params : reinterpret_cast<const Weights17<T>*>(h->weights)->p;
+}
+
+// The slot workspace of an entry point, allocated at its first call: per_cu one-wave workgroups per
+// CU, at most the handle's waves; env_name (MPCB_*_SLOTS): fewer slots, so that a small batch
+// strides over them (tests).
+template <class T>
+static int ensure_slots(mpcb_handle* h, SlotWs& ws, int64_t slot_elems, int per_cu, const char* env_name,
+                        const char* what) {
+  if (ws.mem) return MPCB_OK;
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+  int64_t grid = (int64_t)cus * per_cu;
+  const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
+  if (const char* e = getenv(env_name))
+    if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
+  if (grid > waves) grid = waves;
+  if (grid < 1) grid = 1;
+  const size_t bytes = (size_t)slot_elems * sizeof(T) * (size_t)grid;
+  const hipError_t e = hipMalloc(&ws.mem, bytes);
+  if (e != hipSuccess) {
+    ws.mem = nullptr;
+    return fail(MPCB_E_NOMEM, "%s workspace %zu bytes: %s", what, bytes, hipGetErrorString(e));
+  }
+  ws.grid = (int)grid;
+  return MPCB_OK;
+}
+
+// launch grid over a slot workspace: a workgroup per wave of the batch, at most the resident slots
+static int slot_grid(const SlotWs& ws, int64_t B) {
+  const int64_t waves = (B + GROUPS - 1) / GROUPS;
+  return (int)(waves < ws.grid ? waves : ws.grid);
+}
 
 // A 17/6 call over B instances may only read parameter rows that exist (mpcb_set_params count).
 static int check_params(const mpcb_handle* h, int64_t B) {
@@ -508,10 +571,9 @@ extern "C" int mpcb_destroy(mpcb_handle* h) {
   (void)hipFree(h->weights);
   if (h->qp_stats) (void)hipFree(h->qp_stats);
   if (h->u_scratch) (void)hipFree(h->u_scratch);
-  if (h->vjp_scratch) (void)hipFree(h->vjp_scratch);
   if (h->vjp17_scratch) (void)hipFree(h->vjp17_scratch);
-  if (h->gains_scratch) (void)hipFree(h->gains_scratch);
-  if (h->pw_scratch) (void)hipFree(h->pw_scratch);
+  for (SlotWs* ws : {&h->vjp_ws, &h->gains_ws, &h->pw_ws})
+    if (ws->mem) (void)hipFree(ws->mem);
   delete h;
   return MPCB_OK;
 }
@@ -563,7 +625,7 @@ static int solve_body(mpcb_handle* h, int64_t B, int mode, const void* x0, int64
     a.mode = mode;
     a.h = (T)h->cfg.dt;
     a.s = (T)h->cfg.cost_scale;
-    if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+    a.M = model_of<T>(h);
     a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
     a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
     a.x0 = (const T*)x0; a.x0_sb = x0_sb;
@@ -596,7 +658,7 @@ static int solve_body(mpcb_handle* h, int64_t B, int mode, const void* x0, int64
     a.mode = mode;
     a.h = (T)h->cfg.dt;
     a.s = (T)h->cfg.cost_scale;
-    if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+    a.M = model_of<T>(h);
     a.W = reinterpret_cast<const Weights<T>*>(h->weights);
     a.x0 = (const T*)x0; a.x0_sb = x0_sb;
     a.xref = (const T*)xref; a.xref_sb = xref_sb;
@@ -664,7 +726,7 @@ static int solve_body(mpcb_handle* h, int64_t B, int mode, const void* x0, int64
   a.max_as_iter = h->cfg.max_as_iter;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = reinterpret_cast<const Weights<T>*>(h->weights);
   a.x0 = (const T*)x0; a.x0_sb = x0_sb;
   a.xref = (const T*)xref; a.xref_sb = xref_sb;
@@ -746,13 +808,16 @@ extern "C" int mpcb_plan_kernels(const mpcb_config* cfg, int64_t max_batch, int6
   // (never dereferenced: a dry run makes no HIP call and launches nothing)
   alignas(16) static double dummy[64];
   void* d = dummy;
+  // the stack handle's pointers were unset.  Never dereferenced either: the carve still forms
+  // addresses past the dummy, which a dry run only tests for null
+  h.scratch = h.weights = d;
   LaunchLog& L = launch_log();
   L.dry = true;
-  int rc = cfg->dtype == MPCB_F64
-               ? solve_impl<double>(&h, B, mode, d, 0, d, d, d, 0, d, 0, nullptr, 0, d, want_traj ? d : nullptr,
-                                    want_traj ? d : nullptr, (int32_t*)d, nullptr)
-               : solve_impl<float>(&h, B, mode, d, 0, d, d, d, 0, d, 0, nullptr, 0, d, want_traj ? d : nullptr,
-                                   want_traj ? d : nullptr, (int32_t*)d, nullptr);
+  const int rc = by_dtype(&h, [&](auto t) {
+    return solve_impl<typename decltype(t)::type>(&h, B, mode, d, 0, d, d, d, 0, d, 0, nullptr, 0, d,
+                                                  want_traj ? d : nullptr, want_traj ? d : nullptr, (int32_t*)d,
+                                                  nullptr);
+  });
   L.dry = false;
   if (rc) return rc;
   return write_kernel_names(h.last_fn, buf, len);
@@ -805,9 +870,7 @@ static int check_strides(int64_t a, int64_t b = 0, int64_t c = 0, int64_t d = 0)
 static int check_solve(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xref,
                        int64_t xref_sb, const void* uref, int64_t uref_sb, int64_t wind_sb, const void* u0,
                        const void* X, const void* U, const int32_t* status) {
-  if (!h) return fail(MPCB_E_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   if (int rc = check_strides(x0_sb, xref_sb, uref_sb, wind_sb)) return rc;
   if (B > 0 && (!x0 || !xref || !uref || !u0 || !status))
     return fail(MPCB_E_INVALID, "x0, xref, uref, u0 and status are required");
@@ -824,11 +887,10 @@ extern "C" int mpcb_solve(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_
   if (!rc) rc = check_params(h, B);
   if (rc || B == 0) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return solve_impl<double>(h, B, MPCB_MODE_ROLLOUT, x0, x0_sb, nullptr, nullptr, xref, xref_sb, uref,
-                              uref_sb, wind, wind_sb, u0, X, U, status, stream);
-  return solve_impl<float>(h, B, MPCB_MODE_ROLLOUT, x0, x0_sb, nullptr, nullptr, xref, xref_sb, uref,
-                           uref_sb, wind, wind_sb, u0, X, U, status, stream);
+  return by_dtype(h, [&](auto t) {
+    return solve_impl<typename decltype(t)::type>(h, B, MPCB_MODE_ROLLOUT, x0, x0_sb, nullptr, nullptr, xref, xref_sb,
+                                                  uref, uref_sb, wind, wind_sb, u0, X, U, status, stream);
+  });
 }
 
 extern "C" int mpcb_solve_iterate(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
@@ -840,11 +902,10 @@ extern "C" int mpcb_solve_iterate(mpcb_handle* h, int64_t B, const void* x0, int
   if (rc || B == 0) return rc;
   if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return solve_impl<double>(h, B, MPCB_MODE_ITERATE, x0, x0_sb, xbar, ubar, xref, xref_sb, uref,
-                              uref_sb, wind, wind_sb, u0, X, U, status, stream);
-  return solve_impl<float>(h, B, MPCB_MODE_ITERATE, x0, x0_sb, xbar, ubar, xref, xref_sb, uref,
-                           uref_sb, wind, wind_sb, u0, X, U, status, stream);
+  return by_dtype(h, [&](auto t) {
+    return solve_impl<typename decltype(t)::type>(h, B, MPCB_MODE_ITERATE, x0, x0_sb, xbar, ubar, xref, xref_sb, uref,
+                                                  uref_sb, wind, wind_sb, u0, X, U, status, stream);
+  });
 }
 
 extern "C" int mpcb_linearize(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* wind,
@@ -856,29 +917,18 @@ extern "C" int mpcb_linearize(mpcb_handle* h, int64_t B, const void* xbar, const
   if (!xbar || !ubar || !A || !Bm || !xnext) return fail(MPCB_E_INVALID, "null array");
   if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->full) {
-    if (wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
-    const int64_t psb = h->params ? h->params_sb : 0, pkb = h->params ? h->params_kb : 0;
-    if (h->cfg.dtype == MPCB_F64) {
-      const double* p = h->params ? (const double*)h->params : reinterpret_cast<const Weights17<double>*>(h->weights)->p;
-      e = launch_linearize17<double>(B, h->cfg.N, h->cfg.dt, h->Md, p, psb, pkb, (const double*)xbar,
-                                     (const double*)ubar, (double*)A, (double*)Bm, (double*)xnext,
-                                     (hipStream_t)stream);
-    } else {
-      const float* p = h->params ? (const float*)h->params : reinterpret_cast<const Weights17<float>*>(h->weights)->p;
-      e = launch_linearize17<float>(B, h->cfg.N, (float)h->cfg.dt, h->Mf, p, psb, pkb, (const float*)xbar,
-                                    (const float*)ubar, (float*)A, (float*)Bm, (float*)xnext,
-                                    (hipStream_t)stream);
+  if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (h->full) {
+      int64_t psb, pkb;
+      const T* p = params17<T>(h, &psb, &pkb);
+      return launch_linearize17<T>(B, h->cfg.N, (T)h->cfg.dt, model_of<T>(h), p, psb, pkb, (const T*)xbar,
+                                   (const T*)ubar, (T*)A, (T*)Bm, (T*)xnext, (hipStream_t)stream);
     }
-  } else if (h->cfg.dtype == MPCB_F64)
-    e = launch_linearize<double>(B, h->cfg.N, h->cfg.dt, h->Md, (const double*)xbar, (const double*)ubar,
-                                 (const double*)wind, wind_sb, (double*)A, (double*)Bm, (double*)xnext,
-                                 (hipStream_t)stream);
-  else
-    e = launch_linearize<float>(B, h->cfg.N, (float)h->cfg.dt, h->Mf, (const float*)xbar, (const float*)ubar,
-                                (const float*)wind, wind_sb, (float*)A, (float*)Bm, (float*)xnext,
-                                (hipStream_t)stream);
+    return launch_linearize<T>(B, h->cfg.N, (T)h->cfg.dt, model_of<T>(h), (const T*)xbar, (const T*)ubar,
+                               (const T*)wind, wind_sb, (T*)A, (T*)Bm, (T*)xnext, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "linearize launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -895,14 +945,10 @@ static int eval_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, c
   a.box_x = h->cfg.box_x;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = h->weights;
   a.p = nullptr; a.p_sb = a.p_kb = 0;
-  if (h->full) {   // the parameters mpcb_solve_iterate reads: mpcb_set_params' array or the defaults
-    a.p = h->params ? (const T*)h->params : reinterpret_cast<const Weights17<T>*>(h->weights)->p;
-    a.p_sb = h->params ? h->params_sb : 0;
-    a.p_kb = h->params ? h->params_kb : 0;
-  }
+  if (h->full) a.p = params17<T>(h, &a.p_sb, &a.p_kb);   // the parameters mpcb_solve_iterate reads
   a.x0 = (const T*)x0; a.x0_sb = x0_sb;
   a.X = (const T*)X; a.U = (const T*)U;
   a.xref = (const T*)xref; a.xref_sb = xref_sb;
@@ -918,9 +964,7 @@ extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_s
                          const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
                          const void* wind, int64_t wind_sb, void* cost, void* res_eq, void* res_ineq,
                          void* res_stat, void* stream) {
-  if (!h) return fail(MPCB_E_INVALID, "null handle");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   if (int rc = check_strides(x0_sb, xref_sb, uref_sb, wind_sb)) return rc;
   if (!cost && !res_eq && !res_ineq && !res_stat) return fail(MPCB_E_INVALID, "no output requested");
   if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
@@ -930,11 +974,10 @@ extern "C" int mpcb_eval(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_s
   if (!X || !U || !xref || !uref) return fail(MPCB_E_INVALID, "X, U, xref and uref are required");
   if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return eval_impl<double>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, cost, res_eq,
-                             res_ineq, res_stat, stream);
-  return eval_impl<float>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, cost, res_eq,
-                          res_ineq, res_stat, stream);
+  return by_dtype(h, [&](auto t) {
+    return eval_impl<typename decltype(t)::type>(h, B, x0, x0_sb, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb,
+                                                 cost, res_eq, res_ineq, res_stat, stream);
+  });
 }
 
 template <class T>
@@ -945,32 +988,15 @@ static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* uba
                     bool pw = false, const void* Qw = nullptr, int64_t Qw_sb = 0, const void* Rw = nullptr,
                     int64_t Rw_sb = 0, const void* QNw = nullptr, int64_t QNw_sb = 0) {
   const int64_t slot = vjp_slot_elems(h->cfg.N);
-  if (!h->vjp_scratch) {
-    // resident slots: at most 8 one-wave workgroups per CU fit (registers: <= 2 waves per SIMD)
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    int64_t grid = (int64_t)cus * 8;
-    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
-    // MPCB_VJP_SLOTS: fewer slots, so that a small batch strides over them (tests)
-    if (const char* e = getenv("MPCB_VJP_SLOTS"))
-      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
-    if (grid > waves) grid = waves;
-    if (grid < 1) grid = 1;
-    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
-    const hipError_t e = hipMalloc(&h->vjp_scratch, bytes);
-    if (e != hipSuccess) {
-      h->vjp_scratch = nullptr;
-      return fail(MPCB_E_NOMEM, "vjp workspace %zu bytes: %s", bytes, hipGetErrorString(e));
-    }
-    h->vjp_grid = (int)grid;
-  }
+  // at most 8 one-wave workgroups per CU fit (registers: <= 2 waves per SIMD)
+  if (int rc = ensure_slots<T>(h, h->vjp_ws, slot, 8, "MPCB_VJP_SLOTS", "vjp")) return rc;
   VjpArgs<T> a;
   a.B = B;
   a.N = h->cfg.N;
   a.box = h->cfg.box_u;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = (const Weights<T>*)h->weights;
   a.xbar = (const T*)xbar; a.ubar = (const T*)ubar; a.U = (const T*)U;
   a.wind = (const T*)wind; a.wind_sb = wind_sb;
@@ -986,11 +1012,9 @@ static int vjp_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* uba
     a.QNw = QNw ? (const T*)QNw : a.W->QN; a.QNw_sb = QNw ? QNw_sb : 0;
   }
   a.status = status;
-  a.scratch = (T*)h->vjp_scratch;
+  a.scratch = (T*)h->vjp_ws.mem;
   a.slot_elems = slot;
-  int64_t grid = (B + GROUPS - 1) / GROUPS;
-  if (grid > h->vjp_grid) grid = h->vjp_grid;
-  const hipError_t e = launch_vjp<T>(a, (int)grid, (hipStream_t)stream);
+  const hipError_t e = launch_vjp<T>(a, slot_grid(h->vjp_ws, B), (hipStream_t)stream);
   if (e != hipSuccess) return fail(MPCB_E_HIP, "vjp launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1002,8 +1026,7 @@ extern "C" int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B, const void* xbar, con
                                 void* gQN, int32_t* status, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (h->full) return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product covers the 12/4 model only");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   const bool wg = gQ || gR || gQN;
   if (h->cfg.box_u && !U) return fail(MPCB_E_INVALID, "U is required on an input-box handle (the active set)");
   if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
@@ -1014,11 +1037,10 @@ extern "C" int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B, const void* xbar, con
     return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
   if (int rc = check_strides(xref_sb, uref_sb, wind_sb)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return vjp_impl<double>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
-                            gxref, guref, gQ, gR, gQN, status, stream);
-  return vjp_impl<float>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
-                         gxref, guref, gQ, gR, gQN, status, stream);
+  return by_dtype(h, [&](auto t) {
+    return vjp_impl<typename decltype(t)::type>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX,
+                                                gU, gx0, gxref, guref, gQ, gR, gQN, status, stream);
+  });
 }
 
 extern "C" int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* X,
@@ -1029,8 +1051,7 @@ extern "C" int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B, const void* xbar, co
                                  void* gR, void* gQN, int32_t* status, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (h->full) return fail(MPCB_E_UNSUPPORTED, "per-instance weights cover the 12/4 model only");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   const bool wg = gQ || gR || gQN;
   if (h->cfg.box_u && !U) return fail(MPCB_E_INVALID, "U is required on an input-box handle (the active set)");
   if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
@@ -1042,11 +1063,11 @@ extern "C" int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B, const void* xbar, co
   if (wg && (!X || !U || !xref || !uref))
     return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return vjp_impl<double>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
-                            gxref, guref, gQ, gR, gQN, status, stream, true, Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb);
-  return vjp_impl<float>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX, gU, gx0,
-                         gxref, guref, gQ, gR, gQN, status, stream, true, Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb);
+  return by_dtype(h, [&](auto t) {
+    return vjp_impl<typename decltype(t)::type>(h, B, xbar, ubar, X, U, xref, xref_sb, uref, uref_sb, wind, wind_sb, gX,
+                                                gU, gx0, gxref, guref, gQ, gR, gQN, status, stream, true, Qw, Qw_sb,
+                                                Rw, Rw_sb, QNw, QNw_sb);
+  });
 }
 
 template <class T>
@@ -1056,26 +1077,9 @@ static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, con
                    const void* QNw, int64_t QNw_sb, const void* model, int64_t model_sb, void* u0, void* X,
                    void* U, int32_t* status, void* stream) {
   const int64_t slot = pw_slot_elems(h->cfg.N, h->cfg.box_u);
-  if (!h->pw_scratch) {
-    // resident slots: at most 6 one-wave workgroups per CU fit (LDS: the exchange rows and the
-    // weights of 4 instances, 24.6 KB in fp64)
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    int64_t grid = (int64_t)cus * 6;
-    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
-    // MPCB_PW_SLOTS: fewer slots, so that a small batch strides over them (tests)
-    if (const char* e = getenv("MPCB_PW_SLOTS"))
-      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
-    if (grid > waves) grid = waves;
-    if (grid < 1) grid = 1;
-    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
-    const hipError_t e = hipMalloc(&h->pw_scratch, bytes);
-    if (e != hipSuccess) {
-      h->pw_scratch = nullptr;
-      return fail(MPCB_E_NOMEM, "per-instance-weight workspace %zu bytes: %s", bytes, hipGetErrorString(e));
-    }
-    h->pw_grid = (int)grid;
-  }
+  // at most 6 one-wave workgroups per CU fit (LDS: the exchange rows and the weights of 4 instances,
+  // 24.6 KB in fp64)
+  if (int rc = ensure_slots<T>(h, h->pw_ws, slot, 6, "MPCB_PW_SLOTS", "per-instance-weight")) return rc;
   PwArgs<T> a;
   a.B = B;
   a.N = h->cfg.N;
@@ -1085,7 +1089,7 @@ static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, con
   if (a.max_as_iter < 1) a.max_as_iter = 1;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = (const Weights<T>*)h->weights;
   a.x0 = (const T*)x0; a.x0_sb = x0_sb;
   a.xref = (const T*)xref; a.xref_sb = xref_sb;
@@ -1099,11 +1103,9 @@ static int pw_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, con
   a.model = (const T*)model; a.model_sb = model ? model_sb : 0;
   a.u0 = (T*)u0; a.X = (T*)X; a.U = (T*)U;
   a.status = status;
-  a.scratch = (T*)h->pw_scratch;
+  a.scratch = (T*)h->pw_ws.mem;
   a.slot_elems = slot;
-  int64_t grid = (B + GROUPS - 1) / GROUPS;
-  if (grid > h->pw_grid) grid = h->pw_grid;
-  const hipError_t e = launch_pw<T>(a, (int)grid, (hipStream_t)stream);
+  const hipError_t e = launch_pw<T>(a, slot_grid(h->pw_ws, B), (hipStream_t)stream);
   if (e != hipSuccess) return fail(MPCB_E_HIP, "per-instance-weight solve launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1136,11 +1138,11 @@ extern "C" int mpcb_solve_iterate_pm(mpcb_handle* h, int64_t B, const void* x0, 
   if (rc || B == 0) return rc;
   if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return pw_impl<double>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb,
-                           Rw, Rw_sb, QNw, QNw_sb, model, model_sb, u0, X, U, status, stream);
-  return pw_impl<float>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb, Qw, Qw_sb, Rw,
-                        Rw_sb, QNw, QNw_sb, model, model_sb, u0, X, U, status, stream);
+  return by_dtype(h, [&](auto t) {
+    return pw_impl<typename decltype(t)::type>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, wind, wind_sb,
+                                               Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb, model, model_sb, u0, X, U, status,
+                                               stream);
+  });
 }
 
 // the handle's model: the kernels this call always launched
@@ -1186,7 +1188,7 @@ static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
   a.N = N;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
   a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
   a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
@@ -1217,8 +1219,7 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
   if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_vjp17 covers the 17/6 model (12/4: mpcb_solve_vjp)");
   if (h->cfg.box_x)
     return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product does not cover the state box (active state rows)");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   const bool wg = gQ || gR || gQN;
   if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
   if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
@@ -1229,11 +1230,10 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
   if (int rc = check_strides(xref_sb, uref_sb)) return rc;
   if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->cfg.dtype == MPCB_F64)
-    return vjp17_impl<double>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref,
-                              guref, gQ, gR, gQN, status, stream);
-  return vjp17_impl<float>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref,
-                           guref, gQ, gR, gQN, status, stream);
+  return by_dtype(h, [&](auto t) {
+    return vjp17_impl<typename decltype(t)::type>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU,
+                                                  gx0, gxref, guref, gQ, gR, gQN, status, stream);
+  });
 }
 
 template <class T>
@@ -1241,32 +1241,15 @@ static int gains_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
                       const uint8_t* fixed, const void* wind, int64_t wind_sb, const void* model,
                       int64_t model_sb, void* K, void* P0, int32_t* status, void* stream) {
   const int64_t slot = gains_slot_elems(h->cfg.N);
-  if (!h->gains_scratch) {
-    // resident slots: mpcb_solve_vjp's count (registers: <= 2 waves per SIMD)
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    int64_t grid = (int64_t)cus * 8;
-    const int64_t waves = (h->max_batch + GROUPS - 1) / GROUPS;
-    // MPCB_GAINS_SLOTS: fewer slots, so that a small batch strides over them (tests)
-    if (const char* e = getenv("MPCB_GAINS_SLOTS"))
-      if (atoll(e) > 0 && atoll(e) < grid) grid = atoll(e);
-    if (grid > waves) grid = waves;
-    if (grid < 1) grid = 1;
-    const size_t bytes = (size_t)slot * sizeof(T) * (size_t)grid;
-    const hipError_t e = hipMalloc(&h->gains_scratch, bytes);
-    if (e != hipSuccess) {
-      h->gains_scratch = nullptr;
-      return fail(MPCB_E_NOMEM, "gains workspace %zu bytes: %s", bytes, hipGetErrorString(e));
-    }
-    h->gains_grid = (int)grid;
-  }
+  // mpcb_solve_vjp's count (registers: <= 2 waves per SIMD)
+  if (int rc = ensure_slots<T>(h, h->gains_ws, slot, 8, "MPCB_GAINS_SLOTS", "gains")) return rc;
   GainsArgs<T> a;
   a.B = B;
   a.N = h->cfg.N;
   a.mask = (fixed || h->cfg.box_u) ? 1 : 0;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = (const Weights<T>*)h->weights;
   a.xbar = (const T*)xbar; a.ubar = (const T*)ubar; a.U = (const T*)U;
   a.fixed = fixed;
@@ -1274,11 +1257,9 @@ static int gains_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
   a.model = (const T*)model; a.model_sb = model ? model_sb : 0;
   a.K = (T*)K; a.P0 = (T*)P0;
   a.status = status;
-  a.scratch = (T*)h->gains_scratch;
+  a.scratch = (T*)h->gains_ws.mem;
   a.slot_elems = slot;
-  int64_t grid = (B + GROUPS - 1) / GROUPS;
-  if (grid > h->gains_grid) grid = h->gains_grid;
-  const hipError_t e = launch_gains<T>(a, (int)grid, (hipStream_t)stream);
+  const hipError_t e = launch_gains<T>(a, slot_grid(h->gains_ws, B), (hipStream_t)stream);
   if (e != hipSuccess) return fail(MPCB_E_HIP, "gains launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1292,7 +1273,7 @@ static int gains17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void*
   a.N = h->cfg.N;
   a.h = (T)h->cfg.dt;
   a.s = (T)h->cfg.cost_scale;
-  if constexpr (sizeof(T) == 8) a.M = h->Md; else a.M = h->Mf;
+  a.M = model_of<T>(h);
   a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
   a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
   a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
@@ -1317,8 +1298,7 @@ static int gains_entry(mpcb_handle* h, int64_t B, const void* xbar, const void* 
   if (h->full && h->cfg.box_x)
     return fail(MPCB_E_UNSUPPORTED, "the gains do not cover the state box (active state rows)");
   if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   if (!K && !P0) return fail(MPCB_E_INVALID, "no output requested");
   if (!h->full && fixed && h->cfg.N > 64)
     return fail(MPCB_E_UNSUPPORTED, "fixed needs N <= 64 on the 12/4 model (N=%d): one mask word per input", h->cfg.N);
@@ -1330,13 +1310,11 @@ static int gains_entry(mpcb_handle* h, int64_t B, const void* xbar, const void* 
   if (h->full)
     if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (h->full) {
-    if (h->cfg.dtype == MPCB_F64) return gains17_impl<double>(h, B, xbar, ubar, fixed, K, P0, status, stream);
-    return gains17_impl<float>(h, B, xbar, ubar, fixed, K, P0, status, stream);
-  }
-  if (h->cfg.dtype == MPCB_F64)
-    return gains_impl<double>(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
-  return gains_impl<float>(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
+  return by_dtype(h, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (h->full) return gains17_impl<T>(h, B, xbar, ubar, fixed, K, P0, status, stream);
+    return gains_impl<T>(h, B, xbar, ubar, U, fixed, wind, wind_sb, model, model_sb, K, P0, status, stream);
+  });
 }
 
 extern "C" int mpcb_solve_gains(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const void* U,
@@ -1364,25 +1342,18 @@ extern "C" int mpcb_sim_step(mpcb_handle* h, int64_t B, const void* x, const voi
   if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
   if (int rc = check_params(h, B)) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->full) {
-    if (wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
-    const int64_t psb = h->params ? h->params_sb : 0;
-    if (h->cfg.dtype == MPCB_F64) {
-      const double* p = h->params ? (const double*)h->params : reinterpret_cast<const Weights17<double>*>(h->weights)->p;
-      e = launch_sim_step17<double>(B, T, h->Md, p, psb, (const double*)x, (const double*)u,
-                                    (double*)x_out, (hipStream_t)stream);
-    } else {
-      const float* p = h->params ? (const float*)h->params : reinterpret_cast<const Weights17<float>*>(h->weights)->p;
-      e = launch_sim_step17<float>(B, (float)T, h->Mf, p, psb, (const float*)x, (const float*)u,
-                                   (float*)x_out, (hipStream_t)stream);
+  if (h->full && wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using S = typename decltype(t)::type;
+    if (h->full) {
+      int64_t psb;
+      const S* p = params17<S>(h, &psb);
+      return launch_sim_step17<S>(B, (S)T, model_of<S>(h), p, psb, (const S*)x, (const S*)u, (S*)x_out,
+                                  (hipStream_t)stream);
     }
-  } else if (h->cfg.dtype == MPCB_F64)
-    e = launch_sim_step<double>(B, T, h->Md, (const double*)x, (const double*)u, (const double*)wind,
-                                wind_sb, (double*)x_out, (hipStream_t)stream);
-  else
-    e = launch_sim_step<float>(B, (float)T, h->Mf, (const float*)x, (const float*)u, (const float*)wind,
-                               wind_sb, (float*)x_out, (hipStream_t)stream);
+    return launch_sim_step<S>(B, (S)T, model_of<S>(h), (const S*)x, (const S*)u, (const S*)wind, wind_sb, (S*)x_out,
+                              (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1400,15 +1371,11 @@ extern "C" int mpcb_sim_step_pm(mpcb_handle* h, int64_t B, const void* x, const 
   if (!x || !u || !x_out) return fail(MPCB_E_INVALID, "null array");
   if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64)
-    e = launch_sim_step_pm<double>(B, T, h->Md.g, (const double*)model, model_sb, (const double*)x,
-                                   (const double*)u, (const double*)wind, wind_sb, (double*)x_out,
-                                   (hipStream_t)stream);
-  else
-    e = launch_sim_step_pm<float>(B, (float)T, h->Mf.g, (const float*)model, model_sb, (const float*)x,
-                                  (const float*)u, (const float*)wind, wind_sb, (float*)x_out,
-                                  (hipStream_t)stream);
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using S = typename decltype(t)::type;
+    return launch_sim_step_pm<S>(B, (S)T, model_of<S>(h).g, (const S*)model, model_sb, (const S*)x, (const S*)u,
+                                 (const S*)wind, wind_sb, (S*)x_out, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_pm launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1418,8 +1385,7 @@ extern "C" int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B, const void* x, const
                                  void* gx, void* gu, void* gwind, void* gmodel, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_sim_step_vjp covers the 12/4 model only");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   if (int rc = check_model_stride(model_sb)) return rc;
   if (int rc = check_strides(wind_sb)) return rc;
   if (!gx && !gu && !gwind && !gmodel) return fail(MPCB_E_INVALID, "no output requested");
@@ -1427,16 +1393,12 @@ extern "C" int mpcb_sim_step_vjp(mpcb_handle* h, int64_t B, const void* x, const
   if (!x || !u || !gxn) return fail(MPCB_E_INVALID, "null array");
   if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64)
-    e = launch_sim_step_vjp<double>(B, T, h->Md, (const double*)model, model_sb, (const double*)x,
-                                    (const double*)u, (const double*)wind, wind_sb, (const double*)gxn,
-                                    (double*)gx, (double*)gu, (double*)gwind, (double*)gmodel,
-                                    (hipStream_t)stream);
-  else
-    e = launch_sim_step_vjp<float>(B, (float)T, h->Mf, (const float*)model, model_sb, (const float*)x,
-                                   (const float*)u, (const float*)wind, wind_sb, (const float*)gxn, (float*)gx,
-                                   (float*)gu, (float*)gwind, (float*)gmodel, (hipStream_t)stream);
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using S = typename decltype(t)::type;
+    return launch_sim_step_vjp<S>(B, (S)T, model_of<S>(h), (const S*)model, model_sb, (const S*)x, (const S*)u,
+                                  (const S*)wind, wind_sb, (const S*)gxn, (S*)gx, (S*)gu, (S*)gwind, (S*)gmodel,
+                                  (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_vjp launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1445,14 +1407,6 @@ static int check_params_stride(int64_t params_sb) {
   if (params_sb < 0 || (params_sb > 0 && params_sb < NP17))
     return fail(MPCB_E_INVALID, "parameter stride %lld: 0 (broadcast) or >= %d", (long long)params_sb, NP17);
   return MPCB_OK;
-}
-
-// The parameter vectors a 17/6 plant step reads when the caller passes none: the handle's
-// mpcb_set_params array at stage 0 with its stride, or the defaults in the weights block.
-template <class T>
-static const T* plant_params(const mpcb_handle* h, int64_t* sb) {
-  *sb = h->params ? h->params_sb : 0;
-  return h->params ? (const T*)h->params : reinterpret_cast<const Weights17<T>*>(h->weights)->p;
 }
 
 extern "C" int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const void* u, const void* params,
@@ -1466,13 +1420,11 @@ extern "C" int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const
   if (!x || !u || !x_out) return fail(MPCB_E_INVALID, "null array");
   if (!(T > 0)) return fail(MPCB_E_INVALID, "T must be > 0");
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64)
-    e = launch_sim_step17<double>(B, T, h->Md, (const double*)params, params_sb, (const double*)x,
-                                  (const double*)u, (double*)x_out, (hipStream_t)stream);
-  else
-    e = launch_sim_step17<float>(B, (float)T, h->Mf, (const float*)params, params_sb, (const float*)x,
-                                 (const float*)u, (float*)x_out, (hipStream_t)stream);
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using S = typename decltype(t)::type;
+    return launch_sim_step17<S>(B, (S)T, model_of<S>(h), (const S*)params, params_sb, (const S*)x, (const S*)u,
+                                (S*)x_out, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_p17 launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1482,8 +1434,7 @@ extern "C" int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B, const void* x, con
                                    void* gparams, void* stream) {
   if (!h) return fail(MPCB_E_INVALID, "null handle");
   if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_sim_step_vjp17 covers the 17/6 model only (12/4: mpcb_sim_step_vjp)");
-  if (B < 0 || B > h->max_batch)
-    return fail(MPCB_E_INVALID, "batch %lld exceeds max_batch %lld", (long long)B, (long long)h->max_batch);
+  if (int rc = check_batch(h, B)) return rc;
   if (int rc = check_params_stride(params_sb)) return rc;
   if (!gx && !gu && !gparams) return fail(MPCB_E_INVALID, "no output requested");
   if (B == 0) return MPCB_OK;
@@ -1493,18 +1444,13 @@ extern "C" int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B, const void* x, con
     if (int rc = check_params(h, B)) return rc;
   }
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64) {
-    const double* p = params ? (const double*)params : plant_params<double>(h, &params_sb);
-    e = launch_sim_step_vjp17<double>(B, T, h->Md, p, params_sb, (const double*)x, (const double*)u,
-                                      (const double*)gxn, (double*)gx, (double*)gu, (double*)gparams,
-                                      (hipStream_t)stream);
-  } else {
-    const float* p = params ? (const float*)params : plant_params<float>(h, &params_sb);
-    e = launch_sim_step_vjp17<float>(B, (float)T, h->Mf, p, params_sb, (const float*)x, (const float*)u,
-                                     (const float*)gxn, (float*)gx, (float*)gu, (float*)gparams,
-                                     (hipStream_t)stream);
-  }
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using S = typename decltype(t)::type;
+    // no parameters given: the handle's at stage 0 with their stride, or the defaults
+    const S* p = params ? (const S*)params : params17<S>(h, &params_sb);
+    return launch_sim_step_vjp17<S>(B, (S)T, model_of<S>(h), p, params_sb, (const S*)x, (const S*)u, (const S*)gxn,
+                                    (S*)gx, (S*)gu, (S*)gparams, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "sim_step_vjp17 launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1519,15 +1465,11 @@ extern "C" int mpcb_gen_inputs(mpcb_handle* h, int64_t B, uint64_t seed, uint64_
   if (ref_kind == 1 && xref_sb == 0) return fail(MPCB_E_INVALID, "sinusoid refs need xref_sb > 0");
   if (h->full) return fail(MPCB_E_UNSUPPORTED, "the synthetic generator covers the 12/4 configs");
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64)
-    e = launch_gen_inputs<double>(B, h->cfg.N, h->cfg.dt, seed, id_offset, ref_kind, (double*)x0,
-                                  (double*)xref, xref_sb, (double*)uref, uref_sb, (double*)wind,
-                                  (hipStream_t)stream);
-  else
-    e = launch_gen_inputs<float>(B, h->cfg.N, (float)h->cfg.dt, seed, id_offset, ref_kind, (float*)x0,
-                                 (float*)xref, xref_sb, (float*)uref, uref_sb, (float*)wind,
-                                 (hipStream_t)stream);
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gen_inputs<T>(B, h->cfg.N, (T)h->cfg.dt, seed, id_offset, ref_kind, (T*)x0, (T*)xref, xref_sb,
+                                (T*)uref, uref_sb, (T*)wind, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "gen_inputs launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }
@@ -1540,13 +1482,10 @@ extern "C" int mpcb_histogram(mpcb_handle* h, int64_t B, const void* u0, double 
   if (B == 0) return MPCB_OK;
   if (!u0 || !counts) return fail(MPCB_E_INVALID, "null array");
   HIP_TRY(hipSetDevice(h->device));
-  hipError_t e;
-  if (h->cfg.dtype == MPCB_F64)
-    e = launch_histogram<double>(B, NU, (const double*)u0, lo, hi, nbins, (unsigned long long*)counts,
-                                 (hipStream_t)stream);
-  else
-    e = launch_histogram<float>(B, NU, (const float*)u0, lo, hi, nbins, (unsigned long long*)counts,
-                                (hipStream_t)stream);
+  const hipError_t e = by_dtype(h, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_histogram<T>(B, NU, (const T*)u0, lo, hi, nbins, (unsigned long long*)counts, (hipStream_t)stream);
+  });
   if (e != hipSuccess) return fail(MPCB_E_HIP, "histogram launch: %s", hipGetErrorString(e));
   return MPCB_OK;
 }

@@ -77,6 +77,43 @@ int main(void) {
   expect_err(mpcb_set_t_blast(NULL, 1.0), "set_t_blast(null handle)");
   expect_err(mpcb_quat_ops(-1, NULL, NULL, NULL, NULL, NULL, NULL), "quat_ops(B=-1)");
   expect_err(mpcb_poc_jacobians(-1, NULL, 0, NULL, 1, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "poc_jacobians(B=-1)");
+  expect_err(mpcb_eval(NULL, 1, buf, 0, buf, buf, buf, 0, buf, 0, NULL, 0, buf, NULL, NULL, NULL, NULL), "eval(null handle)");
+  expect_err(mpcb_solve_vjp(NULL, 1, buf, buf, NULL, NULL, 0, buf, buf, buf, buf, buf, st, NULL), "solve_vjp(null handle)");
+  expect_err(mpcb_solve_vjp_w(NULL, 1, buf, buf, buf, buf, buf, 0, buf, 0, NULL, 0, buf, buf, buf, buf, buf, buf, buf, buf,
+                              st, NULL), "solve_vjp_w(null handle)");
+  expect_err(mpcb_solve_vjp_pw(NULL, 1, buf, buf, buf, buf, buf, 0, buf, 0, NULL, 0, buf, 0, buf, 0, buf, 0, buf, buf, buf,
+                               buf, buf, buf, buf, buf, st, NULL), "solve_vjp_pw(null handle)");
+  expect_err(mpcb_solve_iterate_pw(NULL, 1, buf, 0, buf, buf, buf, 0, buf, 0, NULL, 0, buf, 0, buf, 0, buf, 0, buf, buf,
+                                   buf, st, NULL), "solve_iterate_pw(null handle)");
+  expect_err(mpcb_solve_iterate_pm(NULL, 1, buf, 0, buf, buf, buf, 0, buf, 0, NULL, 0, buf, 0, buf, 0, buf, 0, buf, -1,
+                                   buf, buf, buf, st, NULL), "solve_iterate_pm(null handle, negative stride)");
+  expect_err(mpcb_solve_vjp17(NULL, 1, buf, buf, NULL, buf, buf, buf, 0, buf, 0, buf, buf, buf, buf, buf, buf, buf, buf,
+                              st, NULL), "solve_vjp17(null handle)");
+  expect_err(mpcb_solve_gains(NULL, 1, buf, buf, NULL, NULL, NULL, -1, buf, buf, st, NULL),
+             "solve_gains(null handle, negative stride)");
+  expect_err(mpcb_solve_gains_pm(NULL, 1, buf, buf, NULL, NULL, NULL, 0, buf, -1, buf, buf, st, NULL),
+             "solve_gains_pm(null handle, negative stride)");
+  expect_err(mpcb_sim_step_pm(NULL, 1, buf, buf, NULL, -1, buf, -1, 1.0 / 30, buf, NULL),
+             "sim_step_pm(null handle, negative strides)");
+  expect_err(mpcb_sim_step_vjp(NULL, 1, buf, buf, NULL, 0, buf, 0, 1.0 / 30, buf, buf, buf, NULL, NULL, NULL),
+             "sim_step_vjp(null handle)");
+  expect_err(mpcb_sim_step_p17(NULL, 1, buf, buf, buf, -1, 1.0 / 30, buf, NULL), "sim_step_p17(null handle, negative stride)");
+  expect_err(mpcb_sim_step_vjp17(NULL, 1, buf, buf, buf, 0, 1.0 / 30, buf, buf, buf, NULL, NULL), "sim_step_vjp17(null handle)");
+  /* the dry run: the kernels a solve would launch, in both dtypes, and its refusals */
+  {
+    char names[2048];
+    c = base();
+    if (mpcb_plan_kernels(&c, 4096, 4096, MPCB_MODE_ROLLOUT, 1, names, sizeof names) != MPCB_OK || !names[0]) {
+      printf("FAIL plan_kernels(f64): %s\n", mpcb_last_error()); ++fails;
+    } else printf("ok   plan_kernels(f64) -> %.60s...\n", names);
+    c.dtype = MPCB_F32;
+    if (mpcb_plan_kernels(&c, 4096, 7, MPCB_MODE_ITERATE, 0, names, sizeof names) != MPCB_OK || !names[0]) {
+      printf("FAIL plan_kernels(f32): %s\n", mpcb_last_error()); ++fails;
+    } else printf("ok   plan_kernels(f32) -> %.60s...\n", names);
+    expect_err(mpcb_plan_kernels(&c, 16, 17, MPCB_MODE_ROLLOUT, 1, names, sizeof names), "plan_kernels(B > max_batch)");
+    expect_err(mpcb_plan_kernels(&c, 16, 16, MPCB_MODE_ROLLOUT, 1, names, 4), "plan_kernels(short buffer)");
+    expect_err(mpcb_plan_kernels(NULL, 16, 16, MPCB_MODE_ROLLOUT, 1, names, sizeof names), "plan_kernels(null config)");
+  }
   if (mpcb_workspace_bytes(NULL) != 0 || mpcb_path(NULL) != -1) { printf("FAIL null getters\n"); ++fails; }
   mpcb_destroy(NULL);
   printf(fails ? "capi_host: %d FAILURES\n" : "capi_host: all checks passed\n", fails);
