@@ -430,8 +430,9 @@ int mpcb_solve_gains(mpcb_handle* h, int64_t B,
  * MPCB_E_UNSUPPORTED: a 17/6 handle; an fp32 handle with box_u (the shared-weight fp32 box owes its
  * accuracy to a refinement kernel that has no per-instance variant).  MPCB_E_INVALID: B > max_batch,
  * a negative stride, a missing x0, xbar, ubar, xref, uref, u0 or status.
- * Out of scope: the 17/6 model, rollout mode (mpcb_solve), mpcb_eval and mpcb_solve_gains at
- * per-instance weights, fp32 with the input box, an interior-point fallback, the acados facade.
+ * Out of scope: the 17/6 model (mpcb_solve_iterate_pw17 below), rollout mode (mpcb_solve),
+ * mpcb_eval and mpcb_solve_gains at per-instance weights, fp32 with the input box, an
+ * interior-point fallback, the acados facade.
  */
 int mpcb_solve_iterate_pw(mpcb_handle* h, int64_t B,
                           const void* x0, int64_t x0_sb,
@@ -524,6 +525,68 @@ int mpcb_solve_vjp_pw(mpcb_handle* h, int64_t B,
                       void* gx0, void* gxref, void* guref,
                       void* gQ, void* gR, void* gQN,
                       int32_t* status, void* hip_stream);
+
+/*
+ * mpcb_solve_iterate with the cost weights given per instance, on the 17/6 model: the QP of
+ * mpcb_solve_iterate on a 17/6 handle in which instance b's own Q [17,17], R [6,6] and QN [17,17]
+ * stand in place of the handle's (the stage cost stays s Q_b, s R_b; the terminal cost is QN_b).
+ * The parameters (mpcb_set_params), the boxes, max_as_iter, dt and the model come from the handle.
+ *   Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb   by the rules of mpcb_solve_iterate_pw: DEVICE arrays of the
+ *        handle's dtype, row-major; element strides, 0 broadcasts, a stride may exceed the record (the
+ *        pad is never read), a negative stride is MPCB_E_INVALID; NULL = the handle's own matrix;
+ *        element alignment only; symmetry (and definiteness) is the caller's contract.
+ *   every other argument, the aliasing and the alignment rules: as for mpcb_solve_iterate (no wind)
+ * Both dtypes, and every box mode the handle was created with: none, the input box (Mehrotra in
+ * fp64, adaptive centring in fp32), the input and state box (fp64, with its polish).  The interior
+ * point is the code of mpcb_solve_iterate, so MPCB_STATUS_MINSTEP and MPCB_STATUS_MAXITER mean what
+ * they mean there.  An instance with a non-finite entry in its weights gets MPCB_STATUS_NAN and NaN
+ * in u0, X and U; the other instances keep their bits.
+ * The call runs the handle's own solve pipeline in the handle's workspace and chunks (nothing is
+ * allocated), with the Riccati kernel's per-instance variant: each 16-lane group keeps its
+ * instance's s Q_b, s R_b in its own LDS block.  It writes neither the QP statistics nor the
+ * record of mpcb_last_kernels / mpcb_last_timing.  With all three pointers NULL it launches the
+ * kernels of mpcb_solve_iterate and returns its bits.
+ * MPCB_E_UNSUPPORTED on a 12/4 handle (mpcb_solve_iterate_pw is its counterpart, and keeps refusing
+ * a 17/6 handle).  MPCB_E_INVALID: as for mpcb_solve_iterate, and a negative weight stride.  A
+ * refused call writes nothing.
+ * Out of scope: gains and mpcb_eval at per-instance weights, rollout mode, the acados facade,
+ * per-instance boxes.
+ */
+int mpcb_solve_iterate_pw17(mpcb_handle* h, int64_t B,
+                            const void* x0, int64_t x0_sb,
+                            const void* xbar, const void* ubar,
+                            const void* xref, int64_t xref_sb,
+                            const void* uref, int64_t uref_sb,
+                            const void* Qw, int64_t Qw_sb,
+                            const void* Rw, int64_t Rw_sb,
+                            const void* QNw, int64_t QNw_sb,
+                            void* u0, void* X, void* U, int32_t* status, void* hip_stream);
+
+/*
+ * mpcb_solve_vjp17 at per-instance weights: the product and the weight gradients of a
+ * mpcb_solve_iterate_pw17 step.  The arguments are those of mpcb_solve_vjp17 plus the six weight
+ * arguments of mpcb_solve_iterate_pw17 (same rules).  Instance b's matrices stand in the adjoint
+ * problem: gxref_k = s Q_b dx_k, gxref_N = QN_b dx_N, guref_k = s R_b du_k; gQ, gR and gQN by the
+ * formulas of mpcb_solve_vjp17, per instance (for weights that differ per instance they are the
+ * gradient itself; for a broadcast matrix the caller sums).  The active set as the `fixed` mask,
+ * the workspace, the chunks, the statuses, the refusal of a state-box handle and the NaN rule (the
+ * weights join it) are those of mpcb_solve_vjp17.  With all three weight pointers NULL it launches
+ * the kernels of mpcb_solve_vjp17 and returns its bits.
+ * MPCB_E_UNSUPPORTED on a 12/4 handle and on a box_x handle; MPCB_E_INVALID as for
+ * mpcb_solve_vjp17, and for a negative weight stride.  A refused call writes nothing.
+ */
+int mpcb_solve_vjp_pw17(mpcb_handle* h, int64_t B,
+                        const void* xbar, const void* ubar, const uint8_t* fixed,
+                        const void* X, const void* U,
+                        const void* xref, int64_t xref_sb,
+                        const void* uref, int64_t uref_sb,
+                        const void* Qw, int64_t Qw_sb,
+                        const void* Rw, int64_t Rw_sb,
+                        const void* QNw, int64_t QNw_sb,
+                        const void* gX, const void* gU,
+                        void* gx0, void* gxref, void* guref,
+                        void* gQ, void* gR, void* gQN,
+                        int32_t* status, void* hip_stream);
 
 /*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
@@ -624,8 +687,9 @@ int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const void* u,
  * 17/6 handle).  MPCB_E_INVALID: B > max_batch, a missing x, u or gxn, all three outputs NULL, a
  * parameter stride that is negative or between 1 and 24, T <= 0, params == NULL with a non-broadcast
  * mpcb_set_params array shorter than B.  A refused call writes nothing.
- * Out of scope: weight gradients through a 17/6 closed loop (the weights are installed on the
- * handle); stage-varying plant parameters (the plant step has one stage); gradients with respect to
+ * (Weight gradients through a 17/6 closed loop come from mpcb_solve_vjp_pw17, which takes the
+ * weights as arguments instead of installing them on the handle.)
+ * Out of scope: stage-varying plant parameters (the plant step has one stage); gradients with respect to
  * the controller's mpcb_set_params; the state box; rollout mode.
  */
 int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B,
@@ -713,8 +777,8 @@ int mpcb_poc_jacobians(int64_t B, const double* pose, double stream_velocity, co
  * handles without an input box.
  * "The last solve" is the last accepted mpcb_solve or mpcb_solve_iterate: no other entry point
  * writes the statistics, so they survive any number of later calls of the others.  In particular
- * a boxed mpcb_solve_iterate_pw or mpcb_solve_iterate_pm does not count as a solve here: its
- * active set keeps no statistics, and a read after it still returns those of the last
+ * a boxed mpcb_solve_iterate_pw, mpcb_solve_iterate_pm or mpcb_solve_iterate_pw17 does not count
+ * as a solve here: it keeps no statistics, and a read after it still returns those of the last
  * mpcb_solve / mpcb_solve_iterate, for at most that solve's batch (tests/test_gpu_history.py).
  */
 int mpcb_qp_stats(mpcb_handle* h, int64_t B, int32_t* out, void* hip_stream);

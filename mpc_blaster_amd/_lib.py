@@ -31,7 +31,8 @@ EXPORTS = ('mpcb_create', 'mpcb_destroy', 'mpcb_last_error', 'mpcb_abi_version',
 EXPORTS_PM = ('mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm')
 # ... and the entry points named after the 17/6 model's dimensions (the list above is held to the
 # header's names by a letters-only pattern; tests/test_gpu_vjp17.py checks these)
-EXPORTS_17 = ('mpcb_solve_vjp17', 'mpcb_sim_step_p17', 'mpcb_sim_step_vjp17')
+EXPORTS_17 = ('mpcb_solve_vjp17', 'mpcb_sim_step_p17', 'mpcb_sim_step_vjp17', 'mpcb_solve_iterate_pw17',
+              'mpcb_solve_vjp_pw17')
 # the timing / launch-log slots of the split path (mpcb_last_timing, mpcb_plan_kernels) and of the
 # 17/6 model
 PHASES_12 = ('nominal', 'riccati', 'forward', 'linearise')
@@ -160,6 +161,15 @@ def load(path: str | None = None):
         getattr(lib, name).restype = i32
     lib.mpcb_sim_step_p17.argtypes = [vp, i64, vp, vp, vp, i64, dbl, vp, vp]
     lib.mpcb_sim_step_vjp17.argtypes = [vp, i64, vp, vp, vp, i64, dbl, vp, vp, vp, vp, vp]
+    # (likewise: the per-instance-weight solve and its product on the 17/6 model)
+    for name in ('mpcb_solve_iterate_pw17', 'mpcb_solve_vjp_pw17'):
+        if not hasattr(lib, name):
+            raise LibraryMissing(f'{p} has no {name}: rebuild it (__graft_entry__.build())')
+        getattr(lib, name).restype = i32
+    lib.mpcb_solve_iterate_pw17.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                            vp, vp, vp, vp, vp]
+    lib.mpcb_solve_vjp_pw17.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = lib
     return lib

@@ -131,14 +131,16 @@ class BatchedMPC:
     def _ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
-    def _pw_weights(self, B, Q, R, QN):
+    def _pw_weights(self, B, Q, R, QN, full=False):
         """Per-instance weight arguments as device matrices: a list of (tensor or None, stride) for
         Q, R, QN.  A weight always carries a batch axis: 2-D [B|1, n] holds diagonals, 3-D
         [B|1, n, n] matrices, which are passed as 0.5 (M + M^T).  Built on the device: no host read,
-        no synchronisation."""
+        no synchronisation.  ``full``: the caller is one of the 17/6 entries (``*_pw17``)."""
         torch = _torch()
-        if self.nx == 17:
+        if self.nx == 17 and not full:
             raise ValueError('per-instance weights cover the 12/4 model only')
+        if self.nx != 17 and full:
+            raise ValueError('the pw17 entries cover the 17/6 model (12/4: the Q, R, QN keywords of solve_iterate)')
         out = []
         for name, w, n in (('Q', Q, self.nx), ('R', R, self.nu), ('QN', QN, self.nx)):
             if w is None:
@@ -297,6 +299,49 @@ class BatchedMPC:
         self._u0, self._X, self._U, self._status = u0, X, U, status
         return self._u0
 
+    def solve_iterate_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, out=None):
+        """``solve_iterate`` on a 17/6 handle with the cost weights given per instance
+        (mpcb_solve_iterate_pw17): ``Q`` [B|1,17] or [B|1,17,17], ``R`` [B|1,6] or [B|1,6,6], ``QN``
+        like Q, by the shape rule of ``solve_iterate`` (2-D = diagonals, 3-D = matrices, passed as
+        0.5 (M + M^T)); None = the handle's matrix.  Parameters, boxes and ``max_as_iter`` are the
+        handle's; both dtypes and every box mode.  Built on the device, no synchronisation;
+        ``qp_stats``, ``last_kernels`` and ``last_timing`` do not see the call.  With all three None
+        it returns the bits of ``solve_iterate``.  ``ValueError`` on a 12/4 handle."""
+        if self.nx != 17:
+            raise ValueError('solve_iterate_pw17 covers the 17/6 model (12/4: the Q, R, QN keywords of solve_iterate)')
+        N = self.cfg.N
+        x0, _ = self._dev(x0, (self.nx,), 'x0')
+        B = x0.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f'batch {B} > max_batch {self.max_batch}')
+        xb, _ = self._dev(xbar, (N + 1, self.nx), 'xbar', B)
+        ub, _ = self._dev(ubar, (N, self.nu), 'ubar', B)
+        xr, xr_sb = self._dev(x_ref, (N + 1, self.nx), 'x_ref', B, allow_broadcast=True)
+        ur, ur_sb = self._dev(u_ref, (N, self.nu), 'u_ref', B, allow_broadcast=True)
+        u0, X, U, status = self._outputs(B, True) if out is None else out
+        (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, Q, R, QN, full=True)
+        _lib.check(self.lib.mpcb_solve_iterate_pw17(
+            self._h, B, self._ptr(x0), self.nx, self._ptr(xb), self._ptr(ub), self._ptr(xr), xr_sb,
+            self._ptr(ur), ur_sb, self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb, self._ptr(QNd), QN_sb,
+            self._ptr(u0), self._ptr(X), self._ptr(U), self._ptr(status), self._stream()))
+        self._keep = (x0, xb, ub, xr, ur, Qd, Rd, QNd)
+        self._u0, self._X, self._U, self._status = u0, X, U, status
+        return self._u0
+
+    def solve_iterate_vjp_pw17(self, xbar, ubar, gX=None, gU=None, U=None, X=None, x_ref=None, u_ref=None,
+                               weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None):
+        """``solve_iterate_vjp`` on a 17/6 handle at the per-instance weights a ``solve_iterate_pw17``
+        step was given (mpcb_solve_vjp_pw17): the product and, with ``weights=True``, gQ [B,17,17],
+        gR [B,6,6], gQN [B,17,17] at instance b's matrices, each instance's own (no batch sum).
+        The mask rules (``fixed``, or ``U`` with ``active_tol``) are those of the 17/6 branch of
+        ``solve_iterate_vjp``; ``Q``, ``R``, ``QN`` follow ``solve_iterate_pw17``.  ``ValueError`` on
+        a 12/4 handle; a state-box handle is refused by the library."""
+        if self.nx != 17:
+            raise ValueError('solve_iterate_vjp_pw17 covers the 17/6 model (12/4: the Q, R, QN keywords of '
+                             'solve_iterate_vjp)')
+        return self._solve_iterate_vjp17(xbar, ubar, gX, gU, U, None, X, x_ref, u_ref, weights, fixed,
+                                         active_tol, pw=(Q, R, QN))
+
     def evaluate(self, X, U, x_ref, u_ref, x0=None, wind=None, stat=True):
         """Cost and KKT residuals of the iterate (X [B,N+1,nx], U [B,N,nu]) per instance
         (mpcb_eval; acados ``get_cost()`` / ``get_residuals()``): a dict of [B] device tensors
@@ -439,7 +484,8 @@ class BatchedMPC:
         and defaults; that name is kept for the 17/6 callers)."""
         return self.active_mask17(U, active_tol)
 
-    def _solve_iterate_vjp17(self, xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed, active_tol):
+    def _solve_iterate_vjp17(self, xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed, active_tol,
+                             pw=None):
         torch = _torch()
         if wind is not None:
             raise _lib.MpcbError('mpcb error -4: wind is a 12/4-model extension')
@@ -479,6 +525,17 @@ class BatchedMPC:
             out.update(gQ=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev),
                        gR=torch.empty((B, self.nu, self.nu), dtype=self.dtype, device=dev),
                        gQN=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev))
+        if pw is not None:   # (solve_iterate_vjp_pw17: the weights as arguments)
+            (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, *pw, full=True)
+            self._keep_vjp = (xb, ub, gXd, gUd, Ud, fx, Xd, xr, ur, Qd, Rd, QNd)
+            _lib.check(self.lib.mpcb_solve_vjp_pw17(
+                self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(fx), self._ptr(Xd),
+                self._ptr(Ud if weights else None), self._ptr(xr), xr_sb, self._ptr(ur), ur_sb,
+                self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb, self._ptr(QNd), QN_sb,
+                self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']), self._ptr(out['gxref']),
+                self._ptr(out['guref']), self._ptr(out.get('gQ')), self._ptr(out.get('gR')),
+                self._ptr(out.get('gQN')), self._ptr(out['status']), self._stream()))
+            return out
         self._keep_vjp = (xb, ub, gXd, gUd, Ud, fx, Xd, xr, ur)
         _lib.check(self.lib.mpcb_solve_vjp17(
             self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(fx), self._ptr(Xd),
@@ -567,6 +624,14 @@ class BatchedMPC:
         from .autograd import solve_iterate_diff
         return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN,
                                   active_tol=active_tol, per_instance_weights=per_instance_weights)
+
+    def solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None):
+        """``solve_iterate_pw17`` as a differentiable torch operation: (u0, X, U) whose gradients flow
+        to ``x0``, ``x_ref``, ``u_ref`` and the per-instance weight tensors, each in its own shape
+        (``mpc_blaster_amd.autograd.solve_iterate_diff_pw17``).  The handle's weights stay as they
+        are and nothing synchronises."""
+        from .autograd import solve_iterate_diff_pw17
+        return solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=Q, R=R, QN=QN, active_tol=active_tol)
 
     def set_weights(self, Q=None, R=None, QN=None):
         """New cost weights on this handle (mpcb_set_weights; acados ``cost_set(k, 'W', W)`` with

@@ -56,6 +56,18 @@ Each weight tensor receives its gradient per instance in its own shape, the diag
 other than 0 get zeros.  With the input box the solve is the plain active set of
 ``mpcb_solve_iterate_pw`` (fp64 only).  A 17/6 handle raises ``ValueError``.
 
+Weights per instance on the 17/6 model.  ``solve_iterate_diff_pw17(mpc, x0, xbar, ubar, x_ref, u_ref,
+Q=None, R=None, QN=None, active_tol=None) -> (u0, X, U)`` runs ``BatchedMPC.solve_iterate_pw17`` in the
+forward pass and one ``solve_iterate_vjp_pw17`` call (``mpcb_solve_vjp_pw17``) in the backward pass,
+with the conventions of the paragraph above: the weight tensors follow the batch-axis rule, each
+receives its gradient in its own shape (the diagonal of gQ for a 2-D tensor, the batch sum for a
+``[1, ...]`` tensor), instances with forward status other than 0 get zeros, the handle's weights are
+neither read (when all three are given) nor changed, so two forward graphs on one handle can both
+be differentiated.  The weights-version check is left out exactly when all three are given; the
+model-version check stays (``set_params``).  The mask is derived once by ``active_tol`` as for
+``solve_iterate_diff`` on 17/6; the state-box handle and the f32 boxed handle without ``active_tol``
+are refused as there.  A 12/4 handle raises ``ValueError``.
+
 The plant step.  ``sim_step_diff(mpc, x, u, T=None, wind=None, model=None) -> x_out`` runs
 ``BatchedMPC.sim_step`` in the forward pass and one ``mpcb_sim_step_vjp`` call in the backward pass,
 which requests exactly the outputs whose inputs need a gradient: ``x``, ``u``, ``wind`` and ``model``
@@ -218,6 +230,96 @@ def _function():
     return _FN
 
 
+_PW17 = None
+
+
+def _pw17_function():
+    global _PW17
+    if _PW17 is not None:
+        return _PW17
+    import numpy as np
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolveIteratePw17(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol):
+            N = mpc.cfg.N
+            if mpc.nx != 17:
+                raise ValueError('solve_iterate_diff_pw17 covers the 17/6 model only (12/4: solve_iterate_diff with '
+                                 'per_instance_weights=True)')
+            if mpc.cfg.lbx is not None:
+                raise ValueError('solve_iterate_diff_pw17 does not cover the 17/6 state box: an active state row '
+                                 'is a state equality of the adjoint problem (use a handle without lbx/ubx '
+                                 'when no state row is active)')
+            if mpc.cfg.boxed and active_tol is None and mpc.cfg.dtype != 'f64':
+                raise ValueError('active_tol is required on an f32 17/6 input-box handle')
+            x0d, _ = mpc._dev(x0.detach(), (mpc.nx,), 'x0')
+            B = x0d.shape[0]
+            xb, _ = mpc._dev(xbar.detach() if torch.is_tensor(xbar) else xbar, (N + 1, mpc.nx), 'xbar', B)
+            ub, _ = mpc._dev(ubar.detach() if torch.is_tensor(ubar) else ubar, (N, mpc.nu), 'ubar', B)
+            wts = (Q, R, QN)
+            # (a weight that is no tensor is a constant: an array, on the device once)
+            wdet = [None if w is None else w.detach() if torch.is_tensor(w) else
+                    torch.tensor(np.asarray(w), dtype=mpc.dtype, device=mpc._tdev) for w in wts]
+            u0 = mpc.solve_iterate_pw17(x0d, xb, ub, x_ref.detach(), u_ref.detach(), Q=wdet[0], R=wdet[1],
+                                        QN=wdet[2])   # fresh outputs; the handle keeps its weights
+            X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
+            ctx.mpc = mpc
+            ctx.fixed = mpc.active_mask17(U, active_tol)   # by tolerance, once, from the forward solve's U
+            ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
+            ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
+            ctx.wversion, ctx.mversion = mpc._weights_version, mpc._model_version
+            ctx.wmeta = [(tuple(w.shape), w.dtype) if torch.is_tensor(w) else None for w in wts]
+            ctx.wpresent = [w is not None for w in wdet]
+            ctx.save_for_backward(xb, ub, U, status, X, x_ref.detach(), u_ref.detach(),
+                                  *(w for w in wdet if w is not None))
+            return u0, X, U
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_u0, g_X, g_U):
+            mpc = ctx.mpc
+            xb, ub, U, status, X, xr, ur = ctx.saved_tensors[:7]
+            given = iter(ctx.saved_tensors[7:])
+            pwkw = {k: next(given) for k, p in zip(('Q', 'R', 'QN'), ctx.wpresent) if p}
+            need = ctx.needs_input_grad
+            want_w = any(need[6:9])
+            if not all(ctx.wpresent):   # an omitted matrix is the handle's
+                _same_weights(mpc, ctx.wversion)
+            _same_model(mpc, ctx.mversion)
+            gU = g_U.to(mpc.dtype).clone()
+            gU[:, 0] += g_u0.to(mpc.dtype)
+            if want_w:
+                out = mpc.solve_iterate_vjp_pw17(xb, ub, gX=g_X, gU=gU, U=U, X=X, x_ref=xr, u_ref=ur, weights=True,
+                                                 fixed=ctx.fixed, **pwkw)
+            else:
+                out = mpc.solve_iterate_vjp_pw17(xb, ub, gX=g_X, gU=gU, fixed=ctx.fixed, **pwkw)
+            ok = status == 0
+            grads = []
+            for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
+                g = torch.where(ok.reshape(-1, *([1] * (g.dim() - 1))), g, torch.zeros_like(g))
+                if len(shape) < g.dim() or shape[0] != g.shape[0]:
+                    g = g.sum(dim=0, keepdim=True)   # one row for the whole batch
+                grads.append(g.reshape(shape).to(dt))
+            wgrads = [None, None, None]
+            if want_w:
+                for i, key in enumerate(('gQ', 'gR', 'gQN')):
+                    if ctx.wmeta[i] is None or not need[6 + i]:
+                        continue
+                    shape, dt = ctx.wmeta[i]
+                    g = torch.where(ok.reshape(-1, 1, 1), out[key], torch.zeros_like(out[key]))
+                    g = torch.diagonal(g, dim1=1, dim2=2) if len(shape) == 2 else g
+                    if shape[0] == 1 and g.shape[0] != 1:
+                        g = g.sum(dim=0, keepdim=True)   # one row: the batch sum
+                    wgrads[i] = g.reshape(shape).to(dt)
+            return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
+                    grads[2] if need[5] else None, *wgrads, None)
+
+    _PW17 = SolveIteratePw17
+    return _PW17
+
+
 _SIM = None
 
 
@@ -373,3 +475,15 @@ def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=N
                         for t in (x0, x_ref, u_ref))
     return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol,
                              bool(per_instance_weights))
+
+
+def solve_iterate_diff_pw17(mpc, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None):
+    """(u0 [B,6], X [B,N+1,17], U [B,N,6]) of ``mpc.solve_iterate_pw17``, differentiable with respect to
+    the torch tensors ``x0``, ``x_ref``, ``u_ref`` and the per-instance weight tensors ``Q``, ``R``, ``QN``
+    (2-D diagonals or 3-D matrices with a batch axis; arguments of the solve, not installed on the
+    handle: module docstring).  ``active_tol``: the 17/6 active-set tolerance.  The per-instance
+    status is ``mpc.get_status()``."""
+    import torch
+    x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
+                        for t in (x0, x_ref, u_ref))
+    return _pw17_function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol)

@@ -12,7 +12,7 @@ from .api import BatchedMPC
 
 def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T=None,
                 xbar=None, ubar=None, diagnostics=False, resolve_every: int = 1, feedback: bool = False,
-                active_tol=None, weights=None, model=None, plant_model=None, plant_params=None):
+                active_tol=None, weights=None, model=None, plant_model=None, plant_params=None, weights17=None):
     """Returns (X_sim [B, nsim+1, nx], U_sim [B, nsim, nu], status [B] = max over steps).
 
     ``resolve_every = h > 1`` (h <= N) models a controller slower than the plant: the solve runs
@@ -30,6 +30,11 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     passed to every solve: B candidate weightings run as one closed-loop batch (12/4 model).  Not
     together with ``feedback=True``, whose gains use the handle's weights, nor with
     ``diagnostics``, which evaluates the handle's cost.
+
+    ``weights17``: the same on the 17/6 model (a 12/4 handle raises ``ValueError``): a dict with any of
+    ``Q`` [B|1,17] or [B|1,17,17], ``R`` [B|1,6] or [B|1,6,6], ``QN``; every solve of the loop then goes
+    through ``BatchedMPC.solve_iterate_pw17`` with the handle's parameters and boxes.  Not together
+    with ``feedback=True`` or ``diagnostics``, for the reasons above.
 
     ``model`` and ``plant_model`` (12/4 model): vehicle records [B|1, 14] as
     ``BatchedMPC.pack_model`` builds them, in two roles.  ``model`` is the controller's belief: it
@@ -57,6 +62,14 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
         if diagnostics:
             raise ValueError('diagnostics evaluates the handle\'s cost: not together with weights')
         wkw = {k: v for k, v in weights.items() if v is not None}
+    w17 = _weights17_arg(mpc, weights17, wind)
+    if w17 is not None:
+        if weights is not None:
+            raise ValueError('weights covers the 12/4 model, weights17 the 17/6 model: not both')
+        if feedback:
+            raise ValueError('feedback=True uses the gains of the handle\'s weights: not together with weights17')
+        if diagnostics:
+            raise ValueError('diagnostics evaluates the handle\'s cost: not together with weights17')
     mkw, pkw = {}, {}
     if model is not None or plant_model is not None:
         if mpc.nx == 17:
@@ -80,7 +93,7 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
         if feedback and active_tol is None and mpc.nx == 17 and mpc.cfg.boxed and mpc.cfg.dtype != 'f64':
             raise ValueError('feedback=True on an f32 17/6 input-box handle needs active_tol (solve_iterate_gains)')
         return _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw,
-                          mkw, pkw)
+                          mkw, pkw, w17)
     if active_tol is not None:
         raise ValueError('active_tol belongs to feedback=True')
     dev = f'cuda:{mpc.device}'
@@ -102,7 +115,10 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     diag = {k: torch.empty((B, nsim), dtype=dt, device=dev)
             for k in ('cost', 'res_eq') + (('res_stat',) if stat else ())} if diagnostics else None
     for i in range(nsim):
-        mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
+        if w17 is not None:
+            mpc.solve_iterate_pw17(x, xb, ub, x_ref, u_ref, out=(u0, xb, ub, st), **w17)
+        else:
+            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
         worst = torch.maximum(worst, st)
         Us[:, i] = u0
         if diagnostics:
@@ -116,7 +132,22 @@ def closed_loop(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, wind=None, plant_T
     return Xs, Us, worst
 
 
-def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw, mkw, pkw):
+def _weights17_arg(mpc, weights17, wind):
+    """The ``weights17`` dict of the loops, checked: None, or the keyword arguments of the pw17 entries."""
+    if weights17 is None:
+        return None
+    if mpc.nx != 17:
+        raise ValueError('weights17 covers the 17/6 model only (12/4: weights)')
+    unknown = set(weights17) - {'Q', 'R', 'QN'}
+    if unknown:
+        raise ValueError(f'weights17: unknown keys {sorted(unknown)} (expected Q, R, QN)')
+    if wind is not None:
+        raise ValueError('wind is a 12/4-model extension')
+    return {k: v for k, v in weights17.items() if v is not None}
+
+
+def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedback, active_tol, wkw, mkw, pkw,
+               w17=None):
     """closed_loop with a solve every h plant steps and, optionally, the feedback law between."""
     import numpy as np
     import torch
@@ -147,7 +178,10 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
         if j == 0:
             if feedback:
                 xb0, ub0 = xb.clone(), ub.clone()   # the solve overwrites the iterate in place
-            mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
+            if w17 is not None:
+                mpc.solve_iterate_pw17(x, xb, ub, x_ref, u_ref, out=(u0, xb, ub, st), **w17)
+            else:
+                mpc.solve_iterate(x, xb, ub, x_ref, u_ref, wind=wind, out=(u0, xb, ub, st), **wkw, **mkw)
             worst = torch.maximum(worst, st)
             if feedback:
                 g = mpc.solve_iterate_gains(xb0, ub0, U=ub if box else None, wind=wind, want_P0=False,
@@ -167,7 +201,8 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
 
 
 def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, wind=None, plant_T=None,
-                     weights=None, plant_model=None, warm_start=True, plant_params=None, active_tol=None):
+                     weights=None, plant_model=None, warm_start=True, plant_params=None, active_tol=None,
+                     weights17=None):
     """The loop of ``closed_loop`` as a differentiable torch operation: returns
     (X_sim [B, nsim+1, 12], U_sim [B, nsim, 4], status [B] = max over steps; 17 and 6 on the full
     model).  Each step is ``solve_iterate_diff`` followed by ``sim_step_diff`` (``sim_step_diff17`` on
@@ -194,12 +229,16 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     differentiable in ``x0``, ``x_ref``, ``u_ref`` and ``plant_params`` (the plant's parameter vectors
     [25] or [B|1, 25], ``closed_loop``'s argument; a one-row tensor receives the batch sum).
     ``active_tol`` is ``solve_iterate_diff``'s active-set tolerance.  The controller's parameters are
-    the handle's ``set_params`` and constants.  Refused with ``ValueError``: ``weights`` (on 17/6 they
-    are installed on the handle, so every forward pass would invalidate the previous step's
-    backward), ``plant_model``, ``wind``, and a handle with the state box.  On a 12/4 handle
-    ``plant_params`` and ``active_tol`` are refused."""
+    the handle's ``set_params`` and constants.  ``weights17``: a dict with any of ``Q``, ``R``, ``QN`` as
+    in ``closed_loop``; every solve is then ``solve_iterate_diff_pw17``, whose weights are arguments of
+    the solve and of its backward pass, so the loop is differentiable in the per-instance Q, R, QN as
+    well (a ``[1, ...]`` tensor receives the batch sum), and several forward graphs on one handle can
+    each be differentiated.  Refused with ``ValueError``: ``weights`` (the 12/4 keyword: without
+    per-instance arguments the weights are installed on the handle, so every forward pass would
+    invalidate the previous step's backward), ``plant_model``, ``wind``, and a handle with the state
+    box.  On a 12/4 handle ``plant_params``, ``active_tol`` and ``weights17`` are refused."""
     import torch
-    from .autograd import sim_step_diff, sim_step_diff17, solve_iterate_diff
+    from .autograd import sim_step_diff, sim_step_diff17, solve_iterate_diff, solve_iterate_diff_pw17
     full = mpc.nx == 17
     if full:
         if weights is not None:
@@ -213,6 +252,7 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
             raise ValueError('closed_loop_diff does not cover the 17/6 state box (solve_iterate_diff)')
     elif plant_params is not None or active_tol is not None:
         raise ValueError('plant_params and active_tol belong to the 17/6 model')
+    w17 = _weights17_arg(mpc, weights17, wind)
     wkw = {}
     if weights is not None:
         unknown = set(weights) - {'Q', 'R', 'QN'}
@@ -226,7 +266,9 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     worst = torch.zeros((x.shape[0],), dtype=torch.int32, device=dev)
     Xs, Us = [x], []
     for _ in range(nsim):
-        if full:
+        if w17 is not None:
+            u0, X, U = solve_iterate_diff_pw17(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol, **w17)
+        elif full:
             u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol)
         else:
             u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, wind=wind, per_instance_weights=bool(wkw),

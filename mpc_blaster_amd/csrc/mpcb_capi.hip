@@ -613,6 +613,34 @@ extern "C" int mpcb_qp_stats(mpcb_handle* h, int64_t B, int32_t* out, void* stre
   return MPCB_OK;
 }
 
+// The 17/6 solve's kernel arguments but the chunk (b0, nb) and the QP statistics (null here: the
+// kernel guards it)
+template <class T>
+static FullArgs<T> full17_args(const mpcb_handle* h, int mode, const void* x0, int64_t x0_sb, const void* xbar,
+                               const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
+                               int64_t uref_sb, void* u0, void* X, void* U, int32_t* status) {
+  FullArgs<T> a;
+  a.b0 = 0; a.nb = 0;
+  a.N = h->cfg.N;
+  a.mode = mode;
+  a.h = (T)h->cfg.dt;
+  a.s = (T)h->cfg.cost_scale;
+  a.M = model_of<T>(h);
+  a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
+  a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
+  a.x0 = (const T*)x0; a.x0_sb = x0_sb;
+  a.xref = (const T*)xref; a.xref_sb = xref_sb;
+  a.uref = (const T*)uref; a.uref_sb = uref_sb;
+  a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
+  a.u0 = (T*)u0; a.X = (T*)X; a.U = (T*)U; a.status = status;
+  a.ws = (T*)h->scratch;
+  a.box = h->cfg.box_u;
+  a.sbox = h->cfg.box_x;
+  a.max_as_iter = h->cfg.max_as_iter;
+  a.qp_stats = nullptr;
+  return a;
+}
+
 template <class T>
 static int solve_body(mpcb_handle* h, int64_t B, int mode, const void* x0, int64_t x0_sb,
                       const void* xbar, const void* ubar, const void* xref, int64_t xref_sb,
@@ -620,23 +648,7 @@ static int solve_body(mpcb_handle* h, int64_t B, int mode, const void* x0, int64
                       void* u0, void* X, void* U, int32_t* status, void* stream) {
   if (h->full) {
     if (wind) return fail(MPCB_E_UNSUPPORTED, "wind is a 12/4-model extension");
-    FullArgs<T> a;
-    a.N = h->cfg.N;
-    a.mode = mode;
-    a.h = (T)h->cfg.dt;
-    a.s = (T)h->cfg.cost_scale;
-    a.M = model_of<T>(h);
-    a.W = reinterpret_cast<const Weights17<T>*>(h->weights);
-    a.p = (const T*)h->params; a.p_sb = h->params_sb; a.p_kb = h->params_kb;
-    a.x0 = (const T*)x0; a.x0_sb = x0_sb;
-    a.xref = (const T*)xref; a.xref_sb = xref_sb;
-    a.uref = (const T*)uref; a.uref_sb = uref_sb;
-    a.xbar = (const T*)xbar; a.ubar = (const T*)ubar;
-    a.u0 = (T*)u0; a.X = (T*)X; a.U = (T*)U; a.status = status;
-    a.ws = (T*)h->scratch;
-    a.box = h->cfg.box_u;
-    a.sbox = h->cfg.box_x;
-    a.max_as_iter = h->cfg.max_as_iter;
+    FullArgs<T> a = full17_args<T>(h, mode, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, u0, X, U, status);
     a.qp_stats = h->qp_stats;
     int chunk_i = 0;
     for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
@@ -1181,7 +1193,8 @@ template <class T>
 static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar, const uint8_t* fixed,
                       const void* X, const void* U, const void* xref, int64_t xref_sb, const void* uref,
                       int64_t uref_sb, const void* gX, const void* gU, void* gx0, void* gxref, void* guref,
-                      void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
+                      void* gQ, void* gR, void* gQN, int32_t* status, void* stream,
+                      const Pw17<T>* pw = nullptr) {   // (pw: mpcb_solve_vjp_pw17's per-instance weights)
   const int N = h->cfg.N;
   if (int rc = ensure_vjp17_ws<T>(h)) return rc;
   Vjp17Args<T> a;
@@ -1204,7 +1217,7 @@ static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
   for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
     a.b0 = b0;
     a.nb = (B - b0 < h->chunk) ? B - b0 : h->chunk;
-    const hipError_t e = launch_vjp17<T>(a, (hipStream_t)stream);
+    const hipError_t e = pw ? launch_vjp17_pw<T>(a, *pw, (hipStream_t)stream) : launch_vjp17<T>(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(MPCB_E_HIP, "vjp17 launch: %s", hipGetErrorString(e));
   }
   return MPCB_OK;
@@ -1233,6 +1246,78 @@ extern "C" int mpcb_solve_vjp17(mpcb_handle* h, int64_t B, const void* xbar, con
   return by_dtype(h, [&](auto t) {
     return vjp17_impl<typename decltype(t)::type>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU,
                                                   gx0, gxref, guref, gQ, gR, gQN, status, stream);
+  });
+}
+
+// ---- per-instance cost weights on the 17/6 model ------------------------------------------------
+template <class T>
+static int pw17_impl(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar, const void* ubar,
+                     const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb, const void* Qw,
+                     int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw, int64_t QNw_sb, void* u0,
+                     void* X, void* U, int32_t* status, void* stream) {
+  // the handle's solve pipeline and workspace, chunk by chunk; no QP statistics, launch log or timing
+  FullArgs<T> a = full17_args<T>(h, MPCB_MODE_ITERATE, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, u0,
+                                 X, U, status);
+  Pw17<T> pw;
+  const bool own = resolve_pw17<T>(a.W, Qw, Qw_sb, Rw, Rw_sb, QNw, QNw_sb, &pw);
+  for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
+    a.b0 = b0;
+    a.nb = (B - b0 < h->chunk) ? B - b0 : h->chunk;
+    const hipError_t e = launch_full17_pw<T>(a, own ? &pw : nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(MPCB_E_HIP, "per-instance-weight full17 launch: %s", hipGetErrorString(e));
+  }
+  return MPCB_OK;
+}
+
+extern "C" int mpcb_solve_iterate_pw17(mpcb_handle* h, int64_t B, const void* x0, int64_t x0_sb, const void* xbar,
+                                       const void* ubar, const void* xref, int64_t xref_sb, const void* uref,
+                                       int64_t uref_sb, const void* Qw, int64_t Qw_sb, const void* Rw,
+                                       int64_t Rw_sb, const void* QNw, int64_t QNw_sb, void* u0, void* X, void* U,
+                                       int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full)
+    return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_iterate_pw17 covers the 17/6 model (12/4: mpcb_solve_iterate_pw)");
+  int rc = check_solve(h, B, x0, x0_sb, xref, xref_sb, uref, uref_sb, 0, u0, X, U, status);
+  if (!rc) rc = check_strides(Qw_sb, Rw_sb, QNw_sb);
+  if (!rc) rc = check_params(h, B);
+  if (rc || B == 0) return rc;
+  if (!xbar || !ubar) return fail(MPCB_E_INVALID, "xbar and ubar are required");
+  HIP_TRY(hipSetDevice(h->device));
+  return by_dtype(h, [&](auto t) {
+    return pw17_impl<typename decltype(t)::type>(h, B, x0, x0_sb, xbar, ubar, xref, xref_sb, uref, uref_sb, Qw, Qw_sb,
+                                                 Rw, Rw_sb, QNw, QNw_sb, u0, X, U, status, stream);
+  });
+}
+
+extern "C" int mpcb_solve_vjp_pw17(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar,
+                                   const uint8_t* fixed, const void* X, const void* U, const void* xref,
+                                   int64_t xref_sb, const void* uref, int64_t uref_sb, const void* Qw,
+                                   int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw, int64_t QNw_sb,
+                                   const void* gX, const void* gU, void* gx0, void* gxref, void* guref, void* gQ,
+                                   void* gR, void* gQN, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_vjp_pw17 covers the 17/6 model (12/4: mpcb_solve_vjp_pw)");
+  if (h->cfg.box_x)
+    return fail(MPCB_E_UNSUPPORTED, "the vector-Jacobian product does not cover the state box (active state rows)");
+  if (int rc = check_batch(h, B)) return rc;
+  const bool wg = gQ || gR || gQN;
+  if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
+  if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
+  if (int rc = check_strides(xref_sb, uref_sb)) return rc;
+  if (int rc = check_strides(Qw_sb, Rw_sb, QNw_sb)) return rc;
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (wg && (!X || !U || !xref || !uref))
+    return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
+  if (int rc = check_params(h, B)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return by_dtype(h, [&](auto t) {
+    using T = typename decltype(t)::type;
+    Pw17<T> pw;
+    const bool own = resolve_pw17<T>(reinterpret_cast<const Weights17<T>*>(h->weights), Qw, Qw_sb, Rw, Rw_sb, QNw,
+                                     QNw_sb, &pw);
+    return vjp17_impl<T>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref, guref, gQ,
+                         gR, gQN, status, stream, own ? &pw : nullptr);
   });
 }
 

@@ -517,6 +517,29 @@ struct FullArgs {
   int32_t* qp_stats; // boxes: per instance [interior-point iterations, polish passes] (mpcb_qp_stats)
 };
 
+// Per-instance cost weights of the 17/6 calls (mpcb_solve_iterate_pw17, mpcb_solve_vjp_pw17): a
+// second kernel argument of the PW kernels, so FullArgs / Vjp17Args and the shared-weight kernels
+// stay as they are.  Row-major [17,17] / [6,6] / [17,17] at base + b * stride (elements; 0
+// broadcasts).  Never null: the caller resolves a missing matrix to the handle's, stride 0.
+template <class T>
+struct Pw17 {
+  const T* Q = nullptr;  int64_t Q_sb = 0;
+  const T* R = nullptr;  int64_t R_sb = 0;
+  const T* QN = nullptr; int64_t QN_sb = 0;
+};
+
+// The C API's weight arguments -> Pw17: NULL is the handle's matrix for every instance (stride 0,
+// whatever stride came with the NULL).  False when all three are NULL: the shared-weight kernels.
+template <class T>
+inline bool resolve_pw17(const Weights17<T>* W, const void* Qw, int64_t Qw_sb, const void* Rw, int64_t Rw_sb,
+                         const void* QNw, int64_t QNw_sb, Pw17<T>* out) {
+  if (!Qw && !Rw && !QNw) return false;
+  out->Q = Qw ? (const T*)Qw : W->Q;     out->Q_sb = Qw ? Qw_sb : 0;
+  out->R = Rw ? (const T*)Rw : W->R;     out->R_sb = Rw ? Rw_sb : 0;
+  out->QN = QNw ? (const T*)QNw : W->QN; out->QN_sb = QNw ? QNw_sb : 0;
+  return true;
+}
+
 __host__ __device__ constexpr int64_t full17_elems(int N) {
   // XB (N+1)x17 | UB Nx6 | AB N x 23 columns x 17 | KR N x (6x17 + 6) | GP N x 17 |
   // boxes: DX, DDX (N+1)x17 | IP N x 18 | DDU N x 6 | IX (N+1) x 4 x 17 | LC N x 24 | DAX (N+1)x17 | DAU N x 6 | DC N x 48 | GV (N+1) x 24
@@ -683,6 +706,11 @@ template <class T> hipError_t launch_gains17(const Gains17Args<T>& a, hipStream_
 // ev (nullable): 4 events recorded before nominal17, after it, after lin17ws and after riccati17.
 template <class T> hipError_t launch_full17(const FullArgs<T>& a, hipStream_t st, hipEvent_t* ev = nullptr);
 template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_t st);
+// The per-instance-weight pipeline: the same three kernels by plain launches (no launch log, no
+// events), the Riccati kernel's PW variant when pw is given; pw == nullptr: the shared-weight one.
+template <class T> hipError_t launch_full17_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st);
+template <class T> hipError_t launch_riccati17q_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st);
+template <class T> hipError_t launch_vjp17_pw(const Vjp17Args<T>& a, const Pw17<T>& pw, hipStream_t st);
 template <class T>
 hipError_t launch_linearize17(int64_t B, int N, T h, const Model<T>& M, const T* p, int64_t p_sb,
                               int64_t p_kb, const T* xbar, const T* ubar, T* A, T* Bm, T* xnext, hipStream_t st);

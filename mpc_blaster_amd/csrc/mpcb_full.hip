@@ -171,6 +171,13 @@ template <class T> hipError_t launch_full17(const FullArgs<T>& a, hipStream_t st
   if (ev) (void)hipEventRecord(ev[3], st);
   return dry_run() ? hipSuccess : hipGetLastError();
 }
+template <class T> hipError_t launch_full17_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st) {
+  hipLaunchKernelGGL((nominal17q_kernel<T>), dim3((unsigned)((a.nb + 3) / 4)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL((lin17ws_kernel<T>), dim3((unsigned)((a.nb * a.N + GQ17 - 1) / GQ17)), dim3(64), 0, st, a);
+  return launch_riccati17q_pw<T>(a, pw, st);
+}
+template hipError_t launch_full17_pw<double>(const FullArgs<double>&, const Pw17<double>*, hipStream_t);
+template hipError_t launch_full17_pw<float>(const FullArgs<float>&, const Pw17<float>*, hipStream_t);
 template <class T>
 hipError_t launch_linearize17(int64_t B, int N, T h, const Model<T>& M, const T* p, int64_t p_sb,
                               int64_t p_kb, const T* xbar, const T* ubar, T* A, T* Bm, T* xnext,

@@ -216,6 +216,7 @@ struct Ctx {
   Lds<T>& L;
   const T* sQ;        // s * Q (row-major 17 x 17, Q[i][j] at i * 17 + xpos(j): banks), LDS
   const T* sR;        // s * R (6 x 6), LDS
+  const T* QN;        // (PW kernels) the instance's own terminal weight, row-major 17 x 17; else null
   int t, s, z, m;     // lane in the row, owned state, z column, input index (input lanes; else 0)
   bool in, valid;
   int ks;             // 1; 0 once the group is parked (finished, outputs written): every stage-indexed
@@ -310,7 +311,7 @@ __device__ __forceinline__ void load_cur(const Ctx<T>& r, int k, Cur<T>& p) {
 // (nu, side) where the multipliers (lambda_l, lambda_u) were: IP[6 + m], IP[12 + m] and IX rows 2, 3.
 // SBX: the kernel instantiation can carry state rows (the fp64 state-box kernel); the others
 // (the input box alone: Mehrotra in fp64, fp32) compile the state-row code and its registers out.
-template <class T, bool MEH = false, bool POLC = false, bool SBX = true>
+template <class T, bool MEH = false, bool POLC = false, bool SBX = true, bool PW = false>
 __device__ __forceinline__ bool backward(const Ctx<T>& r, T smu, T apend = T(0), bool pol = false) {
   const FullArgs<T>& a = r.a;
   const bool ipm = a.box != 0;
@@ -322,6 +323,8 @@ __device__ __forceinline__ bool backward(const Ctx<T>& r, T smu, T apend = T(0),
   const Weights17<T>& W = *a.W;
   constexpr int KR_N = Ws17<T>::KR_N;
   const uint64_t m_in = lane_mask(in);
+  // (PW: the instance's own terminal weight, Ctx::QN)
+  auto QN = [&](int e) -> T { if constexpr (PW) return r.QN[e]; else return W.QN[e]; };
   // terminal cost: P_N = QN, p_N = QN (x_N - xref_N)
   T Pc[NX17], P88, pj, p8;
   {
@@ -346,11 +349,11 @@ __device__ __forceinline__ bool backward(const Ctx<T>& r, T smu, T apend = T(0),
 #pragma unroll
     for (int i = 0; i < NX17; ++i) {
       const T vi = L.V[xpos(i)];
-      pj += W.QN[s * NX17 + i] * vi;
-      p8 += W.QN[OM * NX17 + i] * vi;
-      Pc[i] = W.QN[i * NX17 + s];
+      pj += QN(s * NX17 + i) * vi;
+      p8 += QN(OM * NX17 + i) * vi;
+      Pc[i] = QN(i * NX17 + s);
     }
-    P88 = W.QN[OM * NX17 + OM];
+    P88 = QN(OM * NX17 + OM);
     wave_lds_sync();
     if constexpr (MEH) {   // p_N for the corrector's vector pass
       T* gv = r.wm.GV + (int64_t)Nq * 24;
@@ -859,11 +862,23 @@ __device__ __forceinline__ bool forward(const Ctx<T>& r, T dxs, T dx8, bool writ
 // owner of the state, the rows of state 8 spread over the lanes by stage (k = 1 + t, 1 + t + 16 ..).
 // MEH (fp64, the input box alone): Mehrotra's predictor-corrector (oracle.ocp._ipm_box_mehrotra)
 // instead of the adaptive centring.
-template <class T, bool BOX, bool MEH>
-__global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
+//
+// One body, two kernels (as_body in mpcb_as.h is the precedent): riccati17q_kernel with the
+// handle's weights staged once per block, and riccati17q_pw_kernel (PW) with instance b's own
+// Q_b, R_b, QN_b (mpcb_solve_iterate_pw17).  PW: sQ / sR are GR blocks of PW17_SQ / PW17_SR
+// elements, one per 16-lane group, staged by the group's own lanes; QN_b is read through Ctx::QN.
+// Block strides: 304 and 48 elements are 32 dwords mod 64 in fp64 and 16 mod 32 in fp32 (Lds'
+// rule): the two instances of a 32-lane half read opposite halves of the bank row.  A non-finite
+// weight of an instance poisons that instance's outputs (the NaN rule).
+constexpr int PW17_SQ = 304, PW17_SR = 48;
+static_assert(PW17_SQ >= NX17 * NX17 && PW17_SR >= NU17 * NU17 && PW17_SQ % 32 == 16 && PW17_SR % 32 == 16,
+              "per-group weight blocks: bank layout");
+
+template <class T, bool BOX, bool MEH, bool PW>
+__device__ __forceinline__ void riccati17q_body(const FullArgs<T>& a, const Pw17<T>& pw) {
   __shared__ Lds<T> lds_all[GR];
-  __shared__ T sQ[NX17 * NX17];
-  __shared__ T sR[NU17 * NU17];
+  __shared__ T sQ[PW ? GR * PW17_SQ : NX17 * NX17];
+  __shared__ T sR[PW ? GR * PW17_SR : NU17 * NU17];
   const int lane = threadIdx.x;
   const int q = lane / LN;
   const int t = lane % LN;
@@ -884,19 +899,51 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
   const bool in = t >= 8 && t < 14;
   const int s = sown(t);
   const int m = in ? t - 8 : 0;
-  for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
-  for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  const T* QNp = nullptr;
+  const T* sQg = sQ;   // this group's s Q, s R: the block's, or (PW) the group's own
+  const T* sRg = sR;
+  bool wbad = false;   // (PW) a non-finite entry in this instance's weights
+  if constexpr (PW) {
+    // the group's own block, staged by its 16 lanes from the clamped b (a padding group reads the
+    // last instance's weights, never past the arrays)
+    const T* Qb = pw.Q + b * pw.Q_sb;
+    const T* Rb = pw.R + b * pw.R_sb;
+    QNp = pw.QN + b * pw.QN_sb;
+    T* const sQw = sQ + q * PW17_SQ;
+    T* const sRw = sR + q * PW17_SR;
+    sQg = sQw;
+    sRg = sRw;
+    T chk = T(0);
+    for (int e = t; e < NX17 * NX17; e += LN) {
+      const T v = Qb[e];
+      chk += v * T(0) + QNp[e] * T(0);
+      sQw[e / NX17 * NX17 + xpos(e % NX17)] = a.s * v;
+    }
+    for (int e = t; e < NU17 * NU17; e += LN) {
+      const T v = Rb[e];
+      chk += v * T(0);
+      sRw[e] = a.s * v;
+    }
+    chk = sum16(chk);
+    wbad = chk != chk;
+    wave_lds_sync();
+  } else {
+    for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
+    for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  }
   __syncthreads();
   Ctx<T> r{a, Ws17<T>(a.ws + c * full17_elems(N), N), WsM17<T>(Ws17<T>(a.ws + c * full17_elems(N), N), N), a.xref + b * a.xref_sb, a.uref + b * a.uref_sb,
-           lds_all[q], sQ, sR, t, s, zcol(t), m, in, valid, 1};
+           lds_all[q], sQg, sRg, QNp, t, s, zcol(t), m, in, valid, 1};
   Lds<T>& L = r.L;
   const T* x0 = a.x0 + b * a.x0_sb;
-  const T dx0s = iterate ? x0[s] - r.w.XB[s] : T(0);
-  const T dx08 = iterate ? x0[OM] - r.w.XB[OM] : T(0);
+  const T qnan_w = __builtin_nan("");
+  // (PW, wbad: the iterate starts from NaN, so every output of the instance is NaN)
+  const T dx0s = (PW && wbad) ? qnan_w : (iterate ? x0[s] - r.w.XB[s] : T(0));
+  const T dx08 = (PW && wbad) ? qnan_w : (iterate ? x0[OM] - r.w.XB[OM] : T(0));
   int32_t st = MPCB_STATUS_OK;
   bool fin;
   if constexpr (!BOX) {
-    if (!backward<T, false, false, false>(r, T(0))) st = MPCB_STATUS_QP_FAIL;
+    if (!backward<T, false, false, false, PW>(r, T(0))) st = MPCB_STATUS_QP_FAIL;
     __syncthreads();   // K and k are read back across lanes
     fin = forward<T, true, false, true>(r, dx0s, dx08, valid);
   } else {
@@ -986,6 +1033,10 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
           xs = xs + r.w.DDX[(int64_t)k * NX17 + s];
           x8 = x8 + r.w.DDX[(int64_t)k * NX17 + OM];
         }
+        if constexpr (PW) {   // (the NaN rule for the instance's weights)
+          xs = wbad ? qnan_w : xs;
+          x8 = wbad ? qnan_w : x8;
+        }
         if (valid && a.X) {
           T* xo = a.X + (b * (int64_t)(N + 1) + k) * NX17;
           xo[s] = r.w.XB[(int64_t)k * NX17 + s] + xs;
@@ -995,6 +1046,7 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
         if (in && k < N) {
           T duk = r.w.IP[(int64_t)k * 18 + m];
           if (POLC && pst == 2) duk = duk + r.w.DDU[(int64_t)k * NU17 + m];
+          if constexpr (PW) duk = wbad ? qnan_w : duk;
           const T uo = r.w.UB[(int64_t)k * NU17 + m] + duk;
           fin = fin && isfin(uo);
           if (valid && a.U) a.U[(b * (int64_t)N + k) * NU17 + m] = uo;
@@ -1070,7 +1122,7 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
       // centring follows the previous step: sigma = clip(1 - alpha, 0.05, 0.9)
       nit += (pst == 0 && !done) ? 1 : 0;
       smu = fmin(T(IPM17_SIGMA_MAX), fmax(T(IPM17_SIGMA_MIN), T(1) - prev_alpha)) * mu;
-      const bool ok_b = backward<T, false, POLC, SBX>(r, smu, apend, pst == 1 || pst == 2);
+      const bool ok_b = backward<T, false, POLC, SBX, PW>(r, smu, apend, pst == 1 || pst == 2);
       apend = T(0);
       if (!ok_b && !done) {
         // a Newton system that lost positive definiteness near the solution: keep the current
@@ -1157,7 +1209,7 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
       // predictor: targets 0 -> the affine direction into DAX / DAU (K, k, the factor of Huu and
       // the stage gradients stay in KR / LC / GV)
       nit += !done ? 1 : 0;
-      const bool ok_b = backward<T, true, false, false>(r, T(0), apend);
+      const bool ok_b = backward<T, true, false, false, PW>(r, T(0), apend);
       apend = T(0);
       if (!ok_b && !done) {
         if (!(mu > ipm_brk)) {
@@ -1357,6 +1409,16 @@ __global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
   if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : st;
 }
 
+template <class T, bool BOX, bool MEH>
+__global__ void __launch_bounds__(64) riccati17q_kernel(FullArgs<T> a) {
+  riccati17q_body<T, BOX, MEH, false>(a, Pw17<T>{});
+}
+
+template <class T, bool BOX, bool MEH>
+__global__ void __launch_bounds__(64) riccati17q_pw_kernel(FullArgs<T> a, Pw17<T> pw) {
+  riccati17q_body<T, BOX, MEH, true>(a, pw);
+}
+
 // ---- mpcb_solve_vjp17: the vector-Jacobian product of the 17/6 RTI step ------------------------
 // At a fixed linearisation point and active set (X, U) of mpcb_solve_iterate is affine in
 // (x0, xref, uref); its transpose applied to (gX, gU) is one more LQ solve over the same [A_k|B_k]
@@ -1414,11 +1476,14 @@ struct PreV {
   uint8_t fx;      // the mask byte of input m (input lanes)
 };
 
-template <class T>
-__global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
+// (vjp17_kernel and vjp17_pw_kernel share vjp17_body as the Riccati kernels share theirs: PW reads
+// instance b's Q_b, R_b from the group's own LDS block and QN_b from its own pointer, and the
+// weights join the check sum of the NaN rule)
+template <class T, bool PW>
+__device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>& pw) {
   __shared__ Lds<T> lds_all[GR];
-  __shared__ T sQ[NX17 * NX17];
-  __shared__ T sR[NU17 * NU17];
+  __shared__ T sQa[PW ? GR * PW17_SQ : NX17 * NX17];
+  __shared__ T sRa[PW ? GR * PW17_SR : NU17 * NU17];
   const int lane = threadIdx.x;
   const int qi = lane / LN;
   const int t = lane % LN;
@@ -1434,8 +1499,31 @@ __global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
   const int s = sown(t);
   const int z = zcol(t);
   const int m = in ? t - 8 : 0;
-  for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
-  for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  T* const sQ = PW ? sQa + qi * PW17_SQ : sQa;   // this group's s Q, s R: the block's, or its own
+  T* const sR = PW ? sRa + qi * PW17_SR : sRa;
+  const T* QNp = nullptr;
+  auto QN = [&](int e) -> T { if constexpr (PW) return QNp[e]; else return W.QN[e]; };
+  T wchk = T(0);   // (PW) v * 0 of the instance's weights
+  if constexpr (PW) {
+    // (riccati17q_body's staging: the group's block, from the clamped b)
+    const T* Qb = pw.Q + b * pw.Q_sb;
+    const T* Rb = pw.R + b * pw.R_sb;
+    QNp = pw.QN + b * pw.QN_sb;
+    for (int e = t; e < NX17 * NX17; e += LN) {
+      const T v = Qb[e];
+      wchk += v * T(0) + QNp[e] * T(0);
+      sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * v;
+    }
+    for (int e = t; e < NU17 * NU17; e += LN) {
+      const T v = Rb[e];
+      wchk += v * T(0);
+      sR[e] = a.s * v;
+    }
+    wave_lds_sync();
+  } else {
+    for (int e = lane; e < NX17 * NX17; e += 64) sQ[e / NX17 * NX17 + xpos(e % NX17)] = a.s * W.Q[e];
+    for (int e = lane; e < NU17 * NU17; e += 64) sR[e] = a.s * W.R[e];
+  }
   __syncthreads();
   const WsV17<T> w(a.ws + c * vjp17_elems(N), N);
   Lds<T>& L = lds_all[qi];
@@ -1452,6 +1540,7 @@ __global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
 
   // ---- the NaN rule: the linearisation's stage values, and what the weight kernel reads later
   T chk = T(0);
+  if constexpr (PW) chk = wchk;
   for (int k = t; k < N; k += LN) chk += w.CK[k];
   if (wg) {
     const T* Xp = a.X + b * (int64_t)(N + 1) * NX17;
@@ -1471,8 +1560,8 @@ __global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
     pj = -gs;
     p8 = -g8;
 #pragma unroll
-    for (int i = 0; i < NX17; ++i) Pc[i] = W.QN[i * NX17 + s];
-    P88 = W.QN[OM * NX17 + OM];
+    for (int i = 0; i < NX17; ++i) Pc[i] = QN(i * NX17 + s);
+    P88 = QN(OM * NX17 + OM);
   }
   auto prefetch = [&](int k, PreV<T>& p) {
     const T* ABk = w.AB + (int64_t)k * NZ17 * NX17;
@@ -1714,13 +1803,23 @@ __global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
     w.DX[(int64_t)N * NX17 + OM] = dx8;
     T wq[LN];
 #pragma unroll
-    for (int tp = 0; tp < LN; ++tp) wq[tp] = W.QN[s * NX17 + sown(tp)];
-    T ox = W.QN[s * NX17 + OM] * dx8;
+    for (int tp = 0; tp < LN; ++tp) wq[tp] = QN(s * NX17 + sown(tp));
+    T ox = QN(s * NX17 + OM) * dx8;
     chain16(ox, dxs, wq);
-    const T ox8 = sum16(W.QN[OM * NX17 + s] * dxs, W.QN[OM * NX17 + OM] * dx8);
+    const T ox8 = sum16(QN(OM * NX17 + s) * dxs, QN(OM * NX17 + OM) * dx8);
     oxs[(int64_t)N * NX17 + s] = bad ? qnan : ox;
     oxs[(int64_t)N * NX17 + OM] = bad ? qnan : ox8;
   }
+}
+
+template <class T>
+__global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
+  vjp17_body<T, false>(a, Pw17<T>{});
+}
+
+template <class T>
+__global__ void __launch_bounds__(64) vjp17_pw_kernel(Vjp17Args<T> a, Pw17<T> pw) {
+  vjp17_body<T, true>(a, pw);
 }
 
 // The weight gradients of one instance per workgroup, from the adjoint trajectory the forward
@@ -2019,6 +2118,40 @@ template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st
 }
 template hipError_t launch_vjp17<double>(const Vjp17Args<double>&, hipStream_t);
 template hipError_t launch_vjp17<float>(const Vjp17Args<float>&, hipStream_t);
+
+// The per-instance-weight calls.  Plain launches: they leave the launch log (mpcb_last_kernels) alone.
+// pw == nullptr (all three weight arguments NULL): the shared-weight kernels themselves.
+template <class T> hipError_t launch_riccati17q_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st) {
+  const dim3 grid((unsigned)((a.nb + q17::GR - 1) / q17::GR));
+  const bool meh = a.box && !a.sbox && sizeof(T) == 8;
+  if (!pw) {
+    if (meh) hipLaunchKernelGGL((q17::riccati17q_kernel<T, true, true>), grid, dim3(64), 0, st, a);
+    else if (a.box) hipLaunchKernelGGL((q17::riccati17q_kernel<T, true, false>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((q17::riccati17q_kernel<T, false, false>), grid, dim3(64), 0, st, a);
+    return hipGetLastError();
+  }
+  if constexpr (sizeof(T) == 8) {   // (Mehrotra is the fp64 input-box kernel: no fp32 instantiation)
+    if (meh) {
+      hipLaunchKernelGGL((q17::riccati17q_pw_kernel<T, true, true>), grid, dim3(64), 0, st, a, *pw);
+      return hipGetLastError();
+    }
+  }
+  if (a.box) hipLaunchKernelGGL((q17::riccati17q_pw_kernel<T, true, false>), grid, dim3(64), 0, st, a, *pw);
+  else hipLaunchKernelGGL((q17::riccati17q_pw_kernel<T, false, false>), grid, dim3(64), 0, st, a, *pw);
+  return hipGetLastError();
+}
+template hipError_t launch_riccati17q_pw<double>(const FullArgs<double>&, const Pw17<double>*, hipStream_t);
+template hipError_t launch_riccati17q_pw<float>(const FullArgs<float>&, const Pw17<float>*, hipStream_t);
+
+template <class T> hipError_t launch_vjp17_pw(const Vjp17Args<T>& a, const Pw17<T>& pw, hipStream_t st) {
+  hipLaunchKernelGGL((q17::vjp17_lin_kernel<T>), dim3((unsigned)((a.nb * a.N + GQ17 - 1) / GQ17)), dim3(64), 0, st, a);
+  hipLaunchKernelGGL((q17::vjp17_pw_kernel<T>), dim3((unsigned)((a.nb + q17::GR - 1) / q17::GR)), dim3(64), 0, st, a, pw);
+  if (a.gQ || a.gR || a.gQN)
+    hipLaunchKernelGGL((q17::vjp17_w_kernel<T>), dim3((unsigned)a.nb), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+template hipError_t launch_vjp17_pw<double>(const Vjp17Args<double>&, const Pw17<double>&, hipStream_t);
+template hipError_t launch_vjp17_pw<float>(const Vjp17Args<float>&, const Pw17<float>&, hipStream_t);
 
 template <class T> hipError_t launch_gains17(const Gains17Args<T>& a, hipStream_t st) {
   const Vjp17Args<T>& v = a.v;
