@@ -333,8 +333,9 @@ int mpcb_solve_vjp_w(mpcb_handle* h, int64_t B,
  *   any of the six outputs may be NULL, not all; gx0, gxref and guref have the same bits with and
  *   without weight outputs
  * MPCB_E_UNSUPPORTED on a 12/4 handle, and on a handle with box_x: an active state row is a state
- * equality of the adjoint problem, which this call does not solve.  A caller who has checked that
- * no state row is active can use a handle with the same definition and no box_x.  MPCB_E_INVALID:
+ * equality of the adjoint problem, which this call does not solve; mpcb_solve_vjp17_sx below does,
+ * and with fixed_x == NULL it is this call for a caller who has checked that no state row is
+ * active.  MPCB_E_INVALID:
  * no cotangent, no output, B > max_batch, a weight output without X, U, xref or uref, a negative
  * stride.  Large batches run in the chunks of the handle's solves; the workspace holds one chunk,
  * is allocated by the first call (MPCB_E_NOMEM) and is not counted by mpcb_workspace_bytes.
@@ -589,6 +590,60 @@ int mpcb_solve_vjp_pw17(mpcb_handle* h, int64_t B,
                         int32_t* status, void* hip_stream);
 
 /*
+ * The 17/6 product with active state rows: mpcb_solve_vjp17 / mpcb_solve_vjp_pw17 through the state
+ * box (fp64).  The arguments are those of mpcb_solve_vjp_pw17 (each weight pointer may be NULL = the
+ * handle's matrix; all three NULL = the handle's weights) and
+ *   fixed_x [B,N+1,17] uint8   nonzero = state row (k, i) is active; stages 0 and N are never read
+ *                              (the solver's state box covers stages 1..N-1).  As with `fixed` the
+ *                              caller derives the set, by a tolerance on X - lbx and ubx - X
+ *                              (BatchedMPC.active_mask17x; the polish of the state-box solve leaves an
+ *                              active row within 1e-10 of its bound).
+ * The adjoint problem gains one family of constraints, dx_k[i] = 0 on every active row (k, i),
+ * 1 <= k <= N-1, beside dx_0 = 0, the dynamics and du_{k,m} = 0 on the clamped inputs.  With mu_k[i]
+ * the multipliers of those rows (zero elsewhere) the outputs are gxref_k = s Q dx_k,
+ * gxref_N = QN dx_N, guref_k = s R du_k, gx0 = nu_0 from nu_N = gX_N - QN dx_N,
+ * nu_k = gX_k - s Q dx_k - mu_k + A_k^T nu_{k+1}, and gQ, gR, gQN by the unchanged formulas on this
+ * (dx, du).  That is J^T (gX, gU) of the polished state-box solve on its active set: the polish
+ * returns the exact solution of the equality-constrained QP on that set, whose KKT matrix is
+ * symmetric.  The product is exact for the masks it is given, on every fp64 17/6 handle with or
+ * without box_u / box_x.
+ * Method: augmented-Lagrangian passes, as in the solver's own polish.  A pass is the Riccati
+ * recursion of mpcb_solve_vjp17 with a penalty of 1e8 on the diagonal of every active row and the
+ * multiplier estimates nu_k (zero at the start) in its gradient, then the forward pass; with
+ * eq = max |dx_k[i]| over the active rows the instance is finished at eq <= 1e-10 max(1, |dx|_inf),
+ * otherwise nu_k[i] += 1e8 dx_k[i] and it runs again, at most 12 passes.
+ * status[B]: MPCB_STATUS_OK; MPCB_STATUS_NAN (the NaN rule of mpcb_solve_vjp17; the mask bytes
+ * cannot be non-finite); MPCB_STATUS_QP_FAIL (a masked input Hessian is not positive definite);
+ * MPCB_STATUS_MAXITER: not converged after 12 passes, the outputs are the last pass's.  That marks
+ * a (nearly) dependent active set, rows that the free inputs cannot hold at zero independently,
+ * at which the solve is not differentiable; no penalty makes such an instance converge.  An
+ * instance without active rows finishes after one pass with the value of mpcb_solve_vjp17.
+ * fixed_x == NULL: the call launches the kernels of mpcb_solve_vjp17 (all weight pointers NULL) or
+ * mpcb_solve_vjp_pw17 and returns their bits, on a box_x handle too, where it means "no state row
+ * is active, as the caller has checked".
+ * The chunks, the first-call workspace (shared with mpcb_solve_vjp17) and the bit-reproducibility
+ * without atomics are those of mpcb_solve_vjp17.
+ * MPCB_E_UNSUPPORTED on a 12/4 handle and on an fp32 handle (a penalty of 1e8 has no meaning in
+ * fp32, and an fp32 handle cannot have box_x); MPCB_E_INVALID as for mpcb_solve_vjp_pw17.  A refused
+ * call writes nothing.
+ * Out of scope: mpcb_solve_gains with state rows (a feedback law under state equalities is another
+ * object), fp32, the 12/4 model, rollout mode.
+ */
+int mpcb_solve_vjp17_sx(mpcb_handle* h, int64_t B,
+                        const void* xbar, const void* ubar,
+                        const uint8_t* fixed, const uint8_t* fixed_x,
+                        const void* X, const void* U,
+                        const void* xref, int64_t xref_sb,
+                        const void* uref, int64_t uref_sb,
+                        const void* Qw, int64_t Qw_sb,
+                        const void* Rw, int64_t Rw_sb,
+                        const void* QNw, int64_t QNw_sb,
+                        const void* gX, const void* gU,
+                        void* gx0, void* gxref, void* guref,
+                        void* gQ, void* gR, void* gQN,
+                        int32_t* status, void* hip_stream);
+
+/*
  * Plant integrator: x_out[b] = Phi(x[b], u[b]) with step T (one RK4 step).  Replaces
  * AcadosSimSolver set('x')/set('u')/solve()/get('x') (simulation_blaster.py:94-104).
  */
@@ -690,7 +745,8 @@ int mpcb_sim_step_p17(mpcb_handle* h, int64_t B, const void* x, const void* u,
  * (Weight gradients through a 17/6 closed loop come from mpcb_solve_vjp_pw17, which takes the
  * weights as arguments instead of installing them on the handle.)
  * Out of scope: stage-varying plant parameters (the plant step has one stage); gradients with respect to
- * the controller's mpcb_set_params; the state box; rollout mode.
+ * the controller's mpcb_set_params; rollout mode.  (The state box: the solve's side of such a loop
+ * is mpcb_solve_vjp17_sx; the plant step itself has no box.)
  */
 int mpcb_sim_step_vjp17(mpcb_handle* h, int64_t B,
                         const void* x, const void* u,

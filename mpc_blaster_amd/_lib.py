@@ -32,7 +32,7 @@ EXPORTS_PM = ('mpcb_sim_step_pm', 'mpcb_solve_iterate_pm', 'mpcb_solve_gains_pm'
 # ... and the entry points named after the 17/6 model's dimensions (the list above is held to the
 # header's names by a letters-only pattern; tests/test_gpu_vjp17.py checks these)
 EXPORTS_17 = ('mpcb_solve_vjp17', 'mpcb_sim_step_p17', 'mpcb_sim_step_vjp17', 'mpcb_solve_iterate_pw17',
-              'mpcb_solve_vjp_pw17')
+              'mpcb_solve_vjp_pw17', 'mpcb_solve_vjp17_sx')
 # the timing / launch-log slots of the split path (mpcb_last_timing, mpcb_plan_kernels) and of the
 # 17/6 model
 PHASES_12 = ('nominal', 'riccati', 'forward', 'linearise')
@@ -169,6 +169,12 @@ def load(path: str | None = None):
     lib.mpcb_solve_iterate_pw17.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                             vp, vp, vp, vp, vp]
     lib.mpcb_solve_vjp_pw17.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    # (likewise: the product with active state rows; mpcb_solve_vjp_pw17's arguments and fixed_x)
+    if not hasattr(lib, 'mpcb_solve_vjp17_sx'):
+        raise LibraryMissing(f'{p} has no mpcb_solve_vjp17_sx: rebuild it (__graft_entry__.build())')
+    lib.mpcb_solve_vjp17_sx.restype = i32
+    lib.mpcb_solve_vjp17_sx.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = lib

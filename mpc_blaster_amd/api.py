@@ -329,18 +329,22 @@ class BatchedMPC:
         return self._u0
 
     def solve_iterate_vjp_pw17(self, xbar, ubar, gX=None, gU=None, U=None, X=None, x_ref=None, u_ref=None,
-                               weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None):
+                               weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None,
+                               fixed_x=None, state_active_tol=None):
         """``solve_iterate_vjp`` on a 17/6 handle at the per-instance weights a ``solve_iterate_pw17``
         step was given (mpcb_solve_vjp_pw17): the product and, with ``weights=True``, gQ [B,17,17],
         gR [B,6,6], gQN [B,17,17] at instance b's matrices, each instance's own (no batch sum).
         The mask rules (``fixed``, or ``U`` with ``active_tol``) are those of the 17/6 branch of
-        ``solve_iterate_vjp``; ``Q``, ``R``, ``QN`` follow ``solve_iterate_pw17``.  ``ValueError`` on
-        a 12/4 handle; a state-box handle is refused by the library."""
+        ``solve_iterate_vjp``; ``Q``, ``R``, ``QN`` follow ``solve_iterate_pw17``.  ``fixed_x`` /
+        ``state_active_tol``: the active state rows, as in ``solve_iterate_vjp`` (mpcb_solve_vjp17_sx
+        with the weight arguments).  ``ValueError`` on a 12/4 handle; without the state-row arguments
+        a state-box handle is refused by the library."""
         if self.nx != 17:
             raise ValueError('solve_iterate_vjp_pw17 covers the 17/6 model (12/4: the Q, R, QN keywords of '
                              'solve_iterate_vjp)')
         return self._solve_iterate_vjp17(xbar, ubar, gX, gU, U, None, X, x_ref, u_ref, weights, fixed,
-                                         active_tol, pw=(Q, R, QN))
+                                         active_tol, pw=(Q, R, QN), fixed_x=fixed_x,
+                                         state_active_tol=state_active_tol)
 
     def evaluate(self, X, U, x_ref, u_ref, x0=None, wind=None, stat=True):
         """Cost and KKT residuals of the iterate (X [B,N+1,nx], U [B,N,nu]) per instance
@@ -370,7 +374,8 @@ class BatchedMPC:
         return out
 
     def solve_iterate_vjp(self, xbar, ubar, gX=None, gU=None, U=None, wind=None, X=None, x_ref=None,
-                          u_ref=None, weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None):
+                          u_ref=None, weights=False, fixed=None, active_tol=None, Q=None, R=None, QN=None,
+                          fixed_x=None, state_active_tol=None):
         """Vector-Jacobian product of ``solve_iterate`` (mpcb_solve_vjp; 17/6: below): with J the
         Jacobian of (X, U) with respect to (x0, x_ref, u_ref) at fixed xbar, ubar, wind, weights
         and active set, returns J^T (gX, gU) as a dict of device tensors ``gx0`` [B,12],
@@ -398,14 +403,24 @@ class BatchedMPC:
         defaults to 1e-6 on an f64 handle (the tolerance the oracle's KKT certificate calls a
         component active at) and has no default on an f32 handle, whose interior point stops near
         mu = 1e-6: omitting it there raises ``ValueError``.  Without ``fixed`` and ``U`` nothing is
-        clamped.  The mask used is returned as ``fixed``.  A handle with the state box is refused;
-        ``wind`` raises as in ``solve_iterate``."""
+        clamped.  The mask used is returned as ``fixed``.  ``wind`` raises as in ``solve_iterate``.
+
+        The 17/6 state box (mpcb_solve_vjp17_sx, f64).  ``fixed_x`` is a bool / uint8 tensor
+        [B,N+1,17], nonzero = state row (k, i) is active (stages 0 and N are never read): the product
+        then holds dx_k[i] = 0 on those rows, exact for the masks it is given on any f64 17/6 handle.
+        Without it, ``state_active_tol`` with ``X`` (the solve's output) on a state-box handle builds
+        the mask by ``active_mask17x``.  Either way the masks used are returned as ``fixed`` and
+        ``fixed_x``, and ``status`` may be 2 (MPCB_STATUS_MAXITER): the rows are (nearly) dependent,
+        the solve is not differentiable there, and the outputs are the last pass's.  Without both
+        arguments a handle with the state box is refused, as before."""
         pw = Q is not None or R is not None or QN is not None
         if self.nx == 17:
             if pw:
                 raise ValueError('per-instance weights cover the 12/4 model only')
             return self._solve_iterate_vjp17(xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed,
-                                             active_tol)
+                                             active_tol, fixed_x=fixed_x, state_active_tol=state_active_tol)
+        if fixed_x is not None or state_active_tol is not None:
+            raise ValueError('fixed_x / state_active_tol belong to the 17/6 model')
         if fixed is not None or active_tol is not None:
             raise ValueError('fixed / active_tol belong to the 17/6 model: the 12/4 product reads its active '
                              'set from U')
@@ -479,13 +494,33 @@ class BatchedMPC:
                              dtype=self.dtype, device=self._tdev)
         return ((U <= lb + active_tol) | (U >= ub - active_tol)).to(torch.uint8).contiguous()
 
+    def active_mask17x(self, X, state_active_tol=None):
+        """The active state rows of ``X`` [B,N+1,17] by tolerance on a 17/6 state-box handle: a uint8
+        tensor [B,N+1,17], 1 where ``X <= lbx + state_active_tol`` or ``X >= ubx - state_active_tol`` on
+        stages 1..N-1 (the rows the solver constrains), 0 on stages 0 and N.  The default is 1e-6, the
+        tolerance of the reference's KKT certificate; the solver's polish leaves an active row within
+        1e-10 of its bound.  None on a handle without the state box."""
+        if self.cfg.lbx is None:
+            return None
+        if state_active_tol is None:
+            state_active_tol = 1e-6
+        torch = _torch()
+        lb = torch.as_tensor(np.broadcast_to(np.asarray(self.cfg.lbx, dtype=np.float64), (self.nx,)).copy(),
+                             dtype=self.dtype, device=self._tdev)
+        ub = torch.as_tensor(np.broadcast_to(np.asarray(self.cfg.ubx, dtype=np.float64), (self.nx,)).copy(),
+                             dtype=self.dtype, device=self._tdev)
+        m = ((X <= lb + state_active_tol) | (X >= ub - state_active_tol)).to(torch.uint8)
+        m[:, 0] = 0
+        m[:, -1] = 0
+        return m.contiguous()
+
     def active_mask(self, U, active_tol=None):
         """The active set of ``U`` [B,N,nu] by tolerance on either model (``active_mask17``'s rule
         and defaults; that name is kept for the 17/6 callers)."""
         return self.active_mask17(U, active_tol)
 
     def _solve_iterate_vjp17(self, xbar, ubar, gX, gU, U, wind, X, x_ref, u_ref, weights, fixed, active_tol,
-                             pw=None):
+                             pw=None, fixed_x=None, state_active_tol=None):
         torch = _torch()
         if wind is not None:
             raise _lib.MpcbError('mpcb error -4: wind is a 12/4-model extension')
@@ -510,6 +545,19 @@ class BatchedMPC:
             fx = self.active_mask17(Ud, active_tol)
         else:
             fx = None
+        # the active state rows (mpcb_solve_vjp17_sx): given, or by tolerance from the solve's X
+        fxx = None
+        if fixed_x is not None:
+            if isinstance(fixed_x, np.ndarray) and not fixed_x.flags.writeable:
+                fixed_x = fixed_x.copy()
+            fxx = torch.as_tensor(fixed_x, device=dev)
+            if tuple(fxx.shape) != (B, N + 1, self.nx):
+                raise ValueError(f'fixed_x: expected shape [{B}, {N + 1}, {self.nx}], got {tuple(fxx.shape)}')
+            fxx = (fxx != 0).to(torch.uint8).contiguous()
+        elif state_active_tol is not None:
+            if X is None:
+                raise ValueError('state_active_tol needs X (the solve\'s output) to build the mask from')
+            fxx = self.active_mask17x(self._dev(X, (N + 1, self.nx), 'X', B)[0], state_active_tol)
         out = dict(gx0=torch.empty((B, self.nx), dtype=self.dtype, device=dev),
                    gxref=torch.empty((B, N + 1, self.nx), dtype=self.dtype, device=dev),
                    guref=torch.empty((B, N, self.nu), dtype=self.dtype, device=dev),
@@ -525,6 +573,19 @@ class BatchedMPC:
             out.update(gQ=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev),
                        gR=torch.empty((B, self.nu, self.nu), dtype=self.dtype, device=dev),
                        gQN=torch.empty((B, self.nx, self.nx), dtype=self.dtype, device=dev))
+        if fxx is not None:   # (the weights as arguments, or all NULL: the handle's)
+            (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = ((None, 0),) * 3 if pw is None else \
+                self._pw_weights(B, *pw, full=True)
+            out['fixed_x'] = fxx
+            self._keep_vjp = (xb, ub, gXd, gUd, Ud, fx, fxx, Xd, xr, ur, Qd, Rd, QNd)
+            _lib.check(self.lib.mpcb_solve_vjp17_sx(
+                self._h, B, self._ptr(xb), self._ptr(ub), self._ptr(fx), self._ptr(fxx), self._ptr(Xd),
+                self._ptr(Ud if weights else None), self._ptr(xr), xr_sb, self._ptr(ur), ur_sb,
+                self._ptr(Qd), Q_sb, self._ptr(Rd), R_sb, self._ptr(QNd), QN_sb,
+                self._ptr(gXd), self._ptr(gUd), self._ptr(out['gx0']), self._ptr(out['gxref']),
+                self._ptr(out['guref']), self._ptr(out.get('gQ')), self._ptr(out.get('gR')),
+                self._ptr(out.get('gQN')), self._ptr(out['status']), self._stream()))
+            return out
         if pw is not None:   # (solve_iterate_vjp_pw17: the weights as arguments)
             (Qd, Q_sb), (Rd, R_sb), (QNd, QN_sb) = self._pw_weights(B, *pw, full=True)
             self._keep_vjp = (xb, ub, gXd, gUd, Ud, fx, Xd, xr, ur, Qd, Rd, QNd)
@@ -613,25 +674,32 @@ class BatchedMPC:
         return out
 
     def solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
-                           active_tol=None, per_instance_weights=False):
+                           active_tol=None, per_instance_weights=False, state_active_tol=None):
         """``solve_iterate`` as a differentiable torch operation: returns (u0, X, U) whose
         gradients flow to ``x0``, ``x_ref`` and ``u_ref`` and, when given, to the weight tensors
         ``Q``, ``R``, ``QN``, which the forward pass installs with ``set_weights`` (see
         ``mpc_blaster_amd.autograd``).  ``active_tol``: the 17/6 active-set tolerance of
         ``solve_iterate_vjp``.  ``per_instance_weights=True`` (12/4): the weight tensors follow the
         batch-axis rule of ``solve_iterate`` and go to the solve as arguments; the handle's weights
-        stay as they are and nothing synchronises."""
+        stay as they are and nothing synchronises.  ``state_active_tol``: on a 17/6 state-box handle,
+        the tolerance of the active state rows (``active_mask17x``); the backward pass is then the
+        product with those rows (mpcb_solve_vjp17_sx), and an instance whose product reports a
+        status other than 0 (a nearly dependent active set) gets zero gradients, like one whose
+        forward status is not 0.  Without it such a handle is refused."""
         from .autograd import solve_iterate_diff
         return solve_iterate_diff(self, x0, xbar, ubar, x_ref, u_ref, wind, Q=Q, R=R, QN=QN,
-                                  active_tol=active_tol, per_instance_weights=per_instance_weights)
+                                  active_tol=active_tol, per_instance_weights=per_instance_weights,
+                                  state_active_tol=state_active_tol)
 
-    def solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None):
+    def solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None,
+                                state_active_tol=None):
         """``solve_iterate_pw17`` as a differentiable torch operation: (u0, X, U) whose gradients flow
         to ``x0``, ``x_ref``, ``u_ref`` and the per-instance weight tensors, each in its own shape
         (``mpc_blaster_amd.autograd.solve_iterate_diff_pw17``).  The handle's weights stay as they
-        are and nothing synchronises."""
+        are and nothing synchronises.  ``state_active_tol``: as in ``solve_iterate_diff``."""
         from .autograd import solve_iterate_diff_pw17
-        return solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=Q, R=R, QN=QN, active_tol=active_tol)
+        return solve_iterate_diff_pw17(self, x0, xbar, ubar, x_ref, u_ref, Q=Q, R=R, QN=QN, active_tol=active_tol,
+                                       state_active_tol=state_active_tol)
 
     def set_weights(self, Q=None, R=None, QN=None):
         """New cost weights on this handle (mpcb_set_weights; acados ``cost_set(k, 'W', W)`` with

@@ -22,8 +22,17 @@ The 17/6 model (``mpcb_solve_vjp17``).  Its boxes are solved by an interior poin
 its bounds and the active set is taken by tolerance: the forward pass derives the mask
 ``(U <= lbu + active_tol) | (U >= ubu - active_tol)`` once (``BatchedMPC.active_mask17``: 1e-6 on an
 f64 handle, required on an f32 one) and the backward pass hands it to the kernel, which is exact
-for that mask.  A handle with the state box is refused (an active state row is not covered), and
-``wind`` raises as in ``solve_iterate``.  The weights work as on 12/4.
+for that mask.  ``wind`` raises as in ``solve_iterate``.  The weights work as on 12/4.
+
+The 17/6 state box (``mpcb_solve_vjp17_sx``).  An active state row is a state equality of the adjoint
+problem, so a handle with ``lbx`` / ``ubx`` is refused unless ``state_active_tol`` is given (f64 only,
+as the state box itself).  Then the forward pass derives both masks once, the inputs' from U and the
+state rows' from X (``BatchedMPC.active_mask17x``: ``X <= lbx + tol`` or ``X >= ubx - tol`` on stages
+1..N-1; the polished rows sit within 1e-10 of their bounds, 1e-6 is the reference's tolerance), and
+the backward pass is the product with those rows held at zero: exact on that active set.  An
+instance gets zero gradients when its forward status is not 0, as everywhere, and also when the
+product's own status is not 0: MPCB_STATUS_MAXITER there marks a (nearly) dependent active set, at
+which the solve is not differentiable.  Without ``state_active_tol`` every call behaves as before.
 
 The weights.  ``Q``, ``R``, ``QN`` are optional torch tensors: a vector (the diagonal) or a
 symmetric matrix.  The weights belong to the handle, so the forward pass installs the value of
@@ -65,7 +74,8 @@ receives its gradient in its own shape (the diagonal of gQ for a 2-D tensor, the
 neither read (when all three are given) nor changed, so two forward graphs on one handle can both
 be differentiated.  The weights-version check is left out exactly when all three are given; the
 model-version check stays (``set_params``).  The mask is derived once by ``active_tol`` as for
-``solve_iterate_diff`` on 17/6; the state-box handle and the f32 boxed handle without ``active_tol``
+``solve_iterate_diff`` on 17/6; the state-box handle without ``state_active_tol`` (with it: the
+paragraph on the state box above, word for word) and the f32 boxed handle without ``active_tol``
 are refused as there.  A 12/4 handle raises ``ValueError``.
 
 The plant step.  ``sim_step_diff(mpc, x, u, T=None, wind=None, model=None) -> x_out`` runs
@@ -119,12 +129,12 @@ def _function():
 
     class SolveIterate(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol, pw):
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol, pw, state_active_tol):
             N = mpc.cfg.N
             full = mpc.nx == 17
             if pw and full:
                 raise ValueError('per_instance_weights covers the 12/4 model only')
-            if full and mpc.cfg.lbx is not None:
+            if full and mpc.cfg.lbx is not None and state_active_tol is None:
                 raise ValueError('solve_iterate_diff does not cover the 17/6 state box: an active state row '
                                  'is a state equality of the adjoint problem (use a handle without lbx/ubx '
                                  'when no state row is active)')
@@ -154,6 +164,8 @@ def _function():
             ctx.full = full
             # (17/6) the active set by tolerance, derived once from the forward solve's U
             ctx.fixed = mpc.active_mask17(U, active_tol) if full else None
+            # ... and, with the state box, the active state rows from its X
+            ctx.fixed_x = mpc.active_mask17x(X, state_active_tol) if full and state_active_tol is not None else None
             ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
             ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
             ctx.has_wind = wd is not None
@@ -177,6 +189,8 @@ def _function():
             wd = ctx.saved_tensors[4] if ctx.has_wind else None
             need = ctx.needs_input_grad
             kw = dict(fixed=ctx.fixed) if ctx.full else dict(wind=wd)
+            if ctx.fixed_x is not None:
+                kw['fixed_x'] = ctx.fixed_x
             want_w = ctx.has_weights and any(need[7:10])
             if not (ctx.pw and all(ctx.wpresent)):
                 _same_weights(mpc, ctx.wversion)
@@ -202,6 +216,8 @@ def _function():
             else:
                 out = mpc.solve_iterate_vjp(xb, ub, gX=g_X, gU=gU, U=None if ctx.full else U, **kw)
             ok = status == 0
+            if ctx.fixed_x is not None:   # (a product that did not converge: module docstring)
+                ok = ok & (out['status'] == 0)
             grads = []
             for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
                 g = torch.where(ok.reshape(-1, *([1] * (g.dim() - 1))), g, torch.zeros_like(g))
@@ -224,7 +240,7 @@ def _function():
                     g = g.sum(dim=0)
                     wgrads[i] = (torch.diagonal(g) if len(shape) == 1 else g).reshape(shape).to(dt)
             return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
-                    grads[2] if need[5] else None, None, *wgrads, None, None)
+                    grads[2] if need[5] else None, None, *wgrads, None, None, None)
 
     _FN = SolveIterate
     return _FN
@@ -243,12 +259,12 @@ def _pw17_function():
 
     class SolveIteratePw17(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol):
+        def forward(ctx, mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol, state_active_tol):
             N = mpc.cfg.N
             if mpc.nx != 17:
                 raise ValueError('solve_iterate_diff_pw17 covers the 17/6 model only (12/4: solve_iterate_diff with '
                                  'per_instance_weights=True)')
-            if mpc.cfg.lbx is not None:
+            if mpc.cfg.lbx is not None and state_active_tol is None:
                 raise ValueError('solve_iterate_diff_pw17 does not cover the 17/6 state box: an active state row '
                                  'is a state equality of the adjoint problem (use a handle without lbx/ubx '
                                  'when no state row is active)')
@@ -267,6 +283,7 @@ def _pw17_function():
             X, U, status = mpc.get_state_trajectory(), mpc.get_input_trajectory(), mpc.get_status()
             ctx.mpc = mpc
             ctx.fixed = mpc.active_mask17(U, active_tol)   # by tolerance, once, from the forward solve's U
+            ctx.fixed_x = None if state_active_tol is None else mpc.active_mask17x(X, state_active_tol)
             ctx.shapes = (tuple(x0.shape), tuple(x_ref.shape), tuple(u_ref.shape))
             ctx.dtypes = (x0.dtype, x_ref.dtype, u_ref.dtype)
             ctx.wversion, ctx.mversion = mpc._weights_version, mpc._model_version
@@ -290,12 +307,16 @@ def _pw17_function():
             _same_model(mpc, ctx.mversion)
             gU = g_U.to(mpc.dtype).clone()
             gU[:, 0] += g_u0.to(mpc.dtype)
+            if ctx.fixed_x is not None:
+                pwkw['fixed_x'] = ctx.fixed_x
             if want_w:
                 out = mpc.solve_iterate_vjp_pw17(xb, ub, gX=g_X, gU=gU, U=U, X=X, x_ref=xr, u_ref=ur, weights=True,
                                                  fixed=ctx.fixed, **pwkw)
             else:
                 out = mpc.solve_iterate_vjp_pw17(xb, ub, gX=g_X, gU=gU, fixed=ctx.fixed, **pwkw)
             ok = status == 0
+            if ctx.fixed_x is not None:   # (a product that did not converge: module docstring)
+                ok = ok & (out['status'] == 0)
             grads = []
             for g, shape, dt in zip((out['gx0'], out['gxref'], out['guref']), ctx.shapes, ctx.dtypes):
                 g = torch.where(ok.reshape(-1, *([1] * (g.dim() - 1))), g, torch.zeros_like(g))
@@ -314,7 +335,7 @@ def _pw17_function():
                         g = g.sum(dim=0, keepdim=True)   # one row: the batch sum
                     wgrads[i] = g.reshape(shape).to(dt)
             return (None, grads[0] if need[1] else None, None, None, grads[1] if need[4] else None,
-                    grads[2] if need[5] else None, *wgrads, None)
+                    grads[2] if need[5] else None, *wgrads, None, None)
 
     _PW17 = SolveIteratePw17
     return _PW17
@@ -462,28 +483,33 @@ def sim_step_diff(mpc, x, u, T=None, wind=None, model=None):
 
 
 def solve_iterate_diff(mpc, x0, xbar, ubar, x_ref, u_ref, wind=None, Q=None, R=None, QN=None,
-                       active_tol=None, per_instance_weights=False):
+                       active_tol=None, per_instance_weights=False, state_active_tol=None):
     """(u0 [B,4], X [B,N+1,12], U [B,N,4]; 17 and 6 on the full model) of ``mpc.solve_iterate``,
     differentiable with respect to the torch tensors ``x0``, ``x_ref`` and ``u_ref`` and, when given, the weight tensors ``Q``, ``R``,
     ``QN`` (vectors or symmetric matrices; installed on the handle by the forward pass, a host
     synchronisation: module docstring).  ``active_tol``: the 17/6 active-set tolerance (module
     docstring).  ``per_instance_weights=True``: the weight tensors carry a batch axis and are arguments
-    of the solve, not installed on the handle (module docstring).  The per-instance status is
-    ``mpc.get_status()``."""
-    import torch
-    x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
-                        for t in (x0, x_ref, u_ref))
-    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol,
-                             bool(per_instance_weights))
-
-
-def solve_iterate_diff_pw17(mpc, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None):
-    """(u0 [B,6], X [B,N+1,17], U [B,N,6]) of ``mpc.solve_iterate_pw17``, differentiable with respect to
-    the torch tensors ``x0``, ``x_ref``, ``u_ref`` and the per-instance weight tensors ``Q``, ``R``, ``QN``
-    (2-D diagonals or 3-D matrices with a batch axis; arguments of the solve, not installed on the
-    handle: module docstring).  ``active_tol``: the 17/6 active-set tolerance.  The per-instance
+    of the solve, not installed on the handle (module docstring).  ``state_active_tol``: the tolerance of
+    the active state rows on a 17/6 state-box handle, which is refused without it; an instance whose
+    product does not converge (status not 0) gets zero gradients (module docstring).  The per-instance
     status is ``mpc.get_status()``."""
     import torch
     x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
                         for t in (x0, x_ref, u_ref))
-    return _pw17_function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol)
+    return _function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, wind, Q, R, QN, active_tol,
+                             bool(per_instance_weights), state_active_tol)
+
+
+def solve_iterate_diff_pw17(mpc, x0, xbar, ubar, x_ref, u_ref, Q=None, R=None, QN=None, active_tol=None,
+                            state_active_tol=None):
+    """(u0 [B,6], X [B,N+1,17], U [B,N,6]) of ``mpc.solve_iterate_pw17``, differentiable with respect to
+    the torch tensors ``x0``, ``x_ref``, ``u_ref`` and the per-instance weight tensors ``Q``, ``R``, ``QN``
+    (2-D diagonals or 3-D matrices with a batch axis; arguments of the solve, not installed on the
+    handle: module docstring).  ``active_tol``: the 17/6 active-set tolerance.  ``state_active_tol``: the
+    tolerance of the active state rows on a state-box handle, which is refused without it; an instance
+    whose product does not converge (status not 0) gets zero gradients.  The per-instance status is
+    ``mpc.get_status()``."""
+    import torch
+    x0, x_ref, u_ref = (t if torch.is_tensor(t) else torch.as_tensor(t, dtype=mpc.dtype, device=mpc._tdev)
+                        for t in (x0, x_ref, u_ref))
+    return _pw17_function().apply(mpc, x0, xbar, ubar, x_ref, u_ref, Q, R, QN, active_tol, state_active_tol)

@@ -202,7 +202,7 @@ def _held_loop(mpc, x0, x_ref, u_ref, nsim, wind, plant_T, xbar, ubar, h, feedba
 
 def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, wind=None, plant_T=None,
                      weights=None, plant_model=None, warm_start=True, plant_params=None, active_tol=None,
-                     weights17=None):
+                     weights17=None, state_active_tol=None):
     """The loop of ``closed_loop`` as a differentiable torch operation: returns
     (X_sim [B, nsim+1, 12], U_sim [B, nsim, 4], status [B] = max over steps; 17 and 6 on the full
     model).  Each step is ``solve_iterate_diff`` followed by ``sim_step_diff`` (``sim_step_diff17`` on
@@ -236,7 +236,10 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     each be differentiated.  Refused with ``ValueError``: ``weights`` (the 12/4 keyword: without
     per-instance arguments the weights are installed on the handle, so every forward pass would
     invalidate the previous step's backward), ``plant_model``, ``wind``, and a handle with the state
-    box.  On a 12/4 handle ``plant_params``, ``active_tol`` and ``weights17`` are refused."""
+    box unless ``state_active_tol`` is given: that is ``solve_iterate_diff``'s tolerance of the active
+    state rows, passed to every solve of the loop, whose backward pass is then the product with
+    state rows (``mpcb_solve_vjp17_sx``).  On a 12/4 handle ``plant_params``, ``active_tol``,
+    ``weights17`` and ``state_active_tol`` are refused."""
     import torch
     from .autograd import sim_step_diff, sim_step_diff17, solve_iterate_diff, solve_iterate_diff_pw17
     full = mpc.nx == 17
@@ -248,9 +251,9 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
             raise ValueError('plant_model covers the 12/4 model only (17/6: plant_params)')
         if wind is not None:
             raise ValueError('wind is a 12/4-model extension')
-        if mpc.cfg.lbx is not None:
+        if mpc.cfg.lbx is not None and state_active_tol is None:
             raise ValueError('closed_loop_diff does not cover the 17/6 state box (solve_iterate_diff)')
-    elif plant_params is not None or active_tol is not None:
+    elif plant_params is not None or active_tol is not None or state_active_tol is not None:
         raise ValueError('plant_params and active_tol belong to the 17/6 model')
     w17 = _weights17_arg(mpc, weights17, wind)
     wkw = {}
@@ -265,11 +268,12 @@ def closed_loop_diff(mpc: BatchedMPC, x0, x_ref, u_ref, nsim: int, xbar, ubar, w
     ub = torch.as_tensor(ubar, dtype=dt, device=dev).detach().clone()
     worst = torch.zeros((x.shape[0],), dtype=torch.int32, device=dev)
     Xs, Us = [x], []
+    skw = {} if state_active_tol is None else dict(state_active_tol=state_active_tol)
     for _ in range(nsim):
         if w17 is not None:
-            u0, X, U = solve_iterate_diff_pw17(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol, **w17)
+            u0, X, U = solve_iterate_diff_pw17(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol, **w17, **skw)
         elif full:
-            u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol)
+            u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, active_tol=active_tol, **skw)
         else:
             u0, X, U = solve_iterate_diff(mpc, x, xb, ub, x_ref, u_ref, wind=wind, per_instance_weights=bool(wkw),
                                           **wkw)

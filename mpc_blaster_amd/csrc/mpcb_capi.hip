@@ -1194,7 +1194,8 @@ static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
                       const void* X, const void* U, const void* xref, int64_t xref_sb, const void* uref,
                       int64_t uref_sb, const void* gX, const void* gU, void* gx0, void* gxref, void* guref,
                       void* gQ, void* gR, void* gQN, int32_t* status, void* stream,
-                      const Pw17<T>* pw = nullptr) {   // (pw: mpcb_solve_vjp_pw17's per-instance weights)
+                      const Pw17<T>* pw = nullptr,     // (pw: mpcb_solve_vjp_pw17's per-instance weights)
+                      const uint8_t* fixed_x = nullptr) {   // (mpcb_solve_vjp17_sx's state rows, fp64)
   const int N = h->cfg.N;
   if (int rc = ensure_vjp17_ws<T>(h)) return rc;
   Vjp17Args<T> a;
@@ -1217,7 +1218,13 @@ static int vjp17_impl(mpcb_handle* h, int64_t B, const void* xbar, const void* u
   for (int64_t b0 = 0; b0 < B; b0 += h->chunk) {
     a.b0 = b0;
     a.nb = (B - b0 < h->chunk) ? B - b0 : h->chunk;
-    const hipError_t e = pw ? launch_vjp17_pw<T>(a, *pw, (hipStream_t)stream) : launch_vjp17<T>(a, (hipStream_t)stream);
+    hipError_t e;
+    if constexpr (sizeof(T) == 8) {
+      e = fixed_x ? launch_vjp17_sx(a, pw, fixed_x, (hipStream_t)stream)
+                  : (pw ? launch_vjp17_pw<T>(a, *pw, (hipStream_t)stream) : launch_vjp17<T>(a, (hipStream_t)stream));
+    } else {
+      e = pw ? launch_vjp17_pw<T>(a, *pw, (hipStream_t)stream) : launch_vjp17<T>(a, (hipStream_t)stream);
+    }
     if (e != hipSuccess) return fail(MPCB_E_HIP, "vjp17 launch: %s", hipGetErrorString(e));
   }
   return MPCB_OK;
@@ -1319,6 +1326,38 @@ extern "C" int mpcb_solve_vjp_pw17(mpcb_handle* h, int64_t B, const void* xbar, 
     return vjp17_impl<T>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref, guref, gQ,
                          gR, gQN, status, stream, own ? &pw : nullptr);
   });
+}
+
+// The product with active state rows.  fixed_x == NULL: the kernels of mpcb_solve_vjp17 /
+// mpcb_solve_vjp_pw17, on a state-box handle too (no row is active, as the caller has checked).
+extern "C" int mpcb_solve_vjp17_sx(mpcb_handle* h, int64_t B, const void* xbar, const void* ubar,
+                                   const uint8_t* fixed, const uint8_t* fixed_x, const void* X, const void* U,
+                                   const void* xref, int64_t xref_sb, const void* uref, int64_t uref_sb,
+                                   const void* Qw, int64_t Qw_sb, const void* Rw, int64_t Rw_sb, const void* QNw,
+                                   int64_t QNw_sb, const void* gX, const void* gU, void* gx0, void* gxref,
+                                   void* guref, void* gQ, void* gR, void* gQN, int32_t* status, void* stream) {
+  if (!h) return fail(MPCB_E_INVALID, "null handle");
+  if (!h->full) return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_vjp17_sx covers the 17/6 model");
+  if (h->cfg.dtype != MPCB_F64)
+    return fail(MPCB_E_UNSUPPORTED, "mpcb_solve_vjp17_sx needs an fp64 handle (the penalty of the state rows)");
+  if (int rc = check_batch(h, B)) return rc;
+  const bool wg = gQ || gR || gQN;
+  if (!gX && !gU) return fail(MPCB_E_INVALID, "no cotangent given");
+  if (!gx0 && !gxref && !guref && !wg) return fail(MPCB_E_INVALID, "no output requested");
+  if (int rc = check_strides(xref_sb, uref_sb)) return rc;
+  if (int rc = check_strides(Qw_sb, Rw_sb, QNw_sb)) return rc;
+  if (B == 0) return MPCB_OK;
+  if (!xbar || !ubar || !status) return fail(MPCB_E_INVALID, "xbar, ubar and status are required");
+  if (wg && (!X || !U || !xref || !uref))
+    return fail(MPCB_E_INVALID, "X, U, xref and uref are required for the weight gradients");
+  if (int rc = check_params(h, B)) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  using T = double;
+  Pw17<T> pw;
+  const bool own = resolve_pw17<T>(reinterpret_cast<const Weights17<T>*>(h->weights), Qw, Qw_sb, Rw, Rw_sb, QNw,
+                                   QNw_sb, &pw);
+  return vjp17_impl<T>(h, B, xbar, ubar, fixed, X, U, xref, xref_sb, uref, uref_sb, gX, gU, gx0, gxref, guref, gQ,
+                       gR, gQN, status, stream, own ? &pw : nullptr, fixed_x);
 }
 
 template <class T>

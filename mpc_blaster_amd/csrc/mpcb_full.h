@@ -638,6 +638,16 @@ constexpr double IPM17_TOL = 1e-12, IPM17_BREAK = 1e-5, IPM17_STALL = 1e-6, IPM1
 // interior point's active set with one active-set change per pass
 constexpr double POL17_RHO = 1e10, POL17_EQ = 1e-10, POL17_FEAS = 1e-10, POL17_ACT = 100.0;
 constexpr int POL17_ITERS = 12;
+// the state rows of the product (mpcb_solve_vjp17_sx): augmented-Lagrangian passes over the adjoint
+// problem, the penalty SX17_RHO on the diagonal of every active state row.  1e8 and not the
+// polish's 1e10: the product has no iterate to absorb the cancellation in P, and a weakly
+// controllable row (a position row one stage ahead) still converges within SX17_ITERS passes
+// (DESIGN.md has the measurement).  A pass ends an instance at eq <= SX17_EQ max(1, |dx|_inf).
+#ifndef MPCB_SX17_RHO   // (-DMPCB_SX17_RHO=...: the variant builds of tools/sx_rho_sweep.py, nothing else)
+#define MPCB_SX17_RHO 1e8
+#endif
+constexpr double SX17_RHO = MPCB_SX17_RHO, SX17_EQ = 1e-10;
+constexpr int SX17_ITERS = 12;
 constexpr double IPM17_SHORT = 1e-2;   // IPM17_SHORT_RUN steps in a row below it: a stalled QP
 constexpr int IPM17_SHORT_RUN = 10;
 // with the state box (the only QPs here that can be infeasible; oracle.ocp IPM_SBOX_SHORT): 7
@@ -675,13 +685,15 @@ struct Vjp17Args {
 // Per-instance workspace carve of the product (Vjp17Args::ws): the linearisation in Ws17::AB's
 // column layout, the gains in Ws17::KR's, the adjoint trajectory (dx, du) for the weight sums, a
 // sink of the same shape as (gxref, guref) for the stores of outputs nobody asked for, and one
-// check value per stage from the linearisation kernel (0, or NaN for a non-finite input).
+// check value per stage from the linearisation kernel (0, or NaN for a non-finite input), and the
+// multiplier estimates of the state rows (vjp17_sx kernels only).
 __host__ __device__ constexpr int64_t vjp17_elems(int N) {
-  return (int64_t)N * (NZ17 * NX17 + NU17 * NX17 + NU17) + 2 * ((int64_t)(N + 1) * NX17 + (int64_t)N * NU17) + N;
+  return (int64_t)N * (NZ17 * NX17 + NU17 * NX17 + NU17) + 2 * ((int64_t)(N + 1) * NX17 + (int64_t)N * NU17) + N +
+         (int64_t)(N + 1) * NX17;
 }
 template <class T>
 struct WsV17 {
-  T *AB, *KR, *DX, *DU, *SK, *CK;
+  T *AB, *KR, *DX, *DU, *SK, *CK, *NU;
   __device__ __forceinline__ WsV17(T* ws, int N) {
     AB = ws;                                     // [N][23][17]
     KR = AB + (int64_t)N * NZ17 * NX17;          // [N][6*17 + 6]
@@ -689,6 +701,7 @@ struct WsV17 {
     DU = DX + (int64_t)(N + 1) * NX17;           // [N][6]
     SK = DU + (int64_t)N * NU17;                 // [N+1][17] | [N][6]
     CK = SK + (int64_t)(N + 1) * NX17 + (int64_t)N * NU17;   // [N]
+    NU = CK + N;                                 // [N+1][17]
   }
 };
 template <class T> hipError_t launch_vjp17(const Vjp17Args<T>& a, hipStream_t st);
@@ -711,6 +724,11 @@ template <class T> hipError_t launch_riccati17q(const FullArgs<T>& a, hipStream_
 template <class T> hipError_t launch_full17_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st);
 template <class T> hipError_t launch_riccati17q_pw(const FullArgs<T>& a, const Pw17<T>* pw, hipStream_t st);
 template <class T> hipError_t launch_vjp17_pw(const Vjp17Args<T>& a, const Pw17<T>& pw, hipStream_t st);
+// mpcb_solve_vjp17_sx: the product with active state rows (fixed_x [B][N+1][17], nonzero = active,
+// never null; a kernel argument of its own, so Vjp17Args and the kernels above stay as they are),
+// fp64 only; pw == nullptr: the handle's weights.
+hipError_t launch_vjp17_sx(const Vjp17Args<double>& a, const Pw17<double>* pw, const uint8_t* fixed_x,
+                           hipStream_t st);
 template <class T>
 hipError_t launch_linearize17(int64_t B, int N, T h, const Model<T>& M, const T* p, int64_t p_sb,
                               int64_t p_kb, const T* xbar, const T* ubar, T* A, T* Bm, T* xnext, hipStream_t st);

@@ -1474,13 +1474,27 @@ struct PreV {
   T a8[5];         // the nonzeros of the implicit column 8
   T gxs, gx8, gum; // gX_k[s], gX_k[8], gU_k[m]
   uint8_t fx;      // the mask byte of input m (input lanes)
+  T nus, nu8;      // (SX) the multiplier estimates of the state rows (k, s) and (k, 8)
+  uint8_t fs, f8;  // (SX) their mask bytes
 };
 
 // (vjp17_kernel and vjp17_pw_kernel share vjp17_body as the Riccati kernels share theirs: PW reads
 // instance b's Q_b, R_b from the group's own LDS block and QN_b from its own pointer, and the
 // weights join the check sum of the NaN rule)
-template <class T, bool PW>
-__device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>& pw) {
+//
+// SX (mpcb_solve_vjp17_sx): active state rows, dx_k[i] = 0 on the rows of fixed_x, by
+// augmented-Lagrangian passes as in the solver's own polish (backward<..., POLC>).  The multiplier
+// estimates nu [N+1][17] live in the call's workspace, zero at the start.  A pass is the stage loop
+// below with SX17_RHO on the diagonal of every active row and nu_k in its gradient, the forward
+// pass (always: dx decides), then eq = max |dx_k[i]| over the active rows; the instance is done at
+// eq <= SX17_EQ max(1, |dx|_inf), otherwise nu_k[i] += SX17_RHO dx_k[i] and it goes again.  The
+// trip count is the wave's: a finished group rides along with its nu frozen, which recomputes its
+// outputs to the same bits (nothing else of its pass depends on the pass number), so no store
+// needs a branch.  SX17_ITERS passes without convergence: MPCB_STATUS_MAXITER, the last pass's
+// outputs.
+template <class T, bool PW, bool SX = false>
+__device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>& pw,
+                                           const uint8_t* fixed_x = nullptr) {
   __shared__ Lds<T> lds_all[GR];
   __shared__ T sQa[PW ? GR * PW17_SQ : NX17 * NX17];
   __shared__ T sRa[PW ? GR * PW17_SR : NU17 * NU17];
@@ -1537,6 +1551,15 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
   const T* gUp = hasU ? a.gU + b * (int64_t)N * NU17 : w.AB;
   const uint8_t* fxp = hasF ? a.fixed + b * (int64_t)N * NU17 : reinterpret_cast<const uint8_t*>(w.AB);
   const uint64_t m_x = lane_mask(hasX), m_u = lane_mask(hasU);
+  const uint8_t* fsp = nullptr;   // (SX) the instance's state mask [N+1][17]
+  if constexpr (SX) {
+    fsp = fixed_x + b * (int64_t)(N + 1) * NX17;
+    for (int k = 0; k <= N; ++k) {
+      w.NU[(int64_t)k * NX17 + s] = T(0);
+      w.NU[(int64_t)k * NX17 + OM] = T(0);   // (the group's 16 lanes, one value)
+    }
+    __syncthreads();
+  }
 
   // ---- the NaN rule: the linearisation's stage values, and what the weight kernel reads later
   T chk = T(0);
@@ -1551,6 +1574,9 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
     for (int i = t; i < N * NU17; i += LN) chk += Up[i] * T(0) + urp[i] * T(0);
   }
 
+  bool qp_ok = true;
+  bool done = false;   // (SX) this group's passes have converged, or cannot
+  for (int pass = 0;; ++pass) {   // (one trip without SX)
   // ---- backward: P_N = QN, p_N = -gX_N
   T Pc[NX17], P88, pj, p8;
   {
@@ -1573,8 +1599,16 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
     p.gx8 = gXp[(int64_t)k * NX17 + OM];
     p.gum = gUp[(int64_t)k * NU17 + m];
     p.fx = fxp[(int64_t)k * NU17 + m];
+    if constexpr (SX) {
+      p.nus = w.NU[(int64_t)k * NX17 + s];
+      p.nu8 = w.NU[(int64_t)k * NX17 + OM];
+      p.fs = fsp[(int64_t)k * NX17 + s];
+      p.f8 = fsp[(int64_t)k * NX17 + OM];
+    } else {
+      p.nus = p.nu8 = T(0);
+      p.fs = p.f8 = 0;
+    }
   };
-  bool qp_ok = true;
   PreV<T> nx;
   prefetch(N - 1, nx);
   for (int k = N - 1; k >= 0; --k) {
@@ -1635,7 +1669,13 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
     }
 #pragma unroll
     for (int i = 0; i < NX17; ++i) Gs[i] += sQ[i * NX17 + xpos(s)];
-    const T hs = (in ? pt : hab) - gxs;   // AB[:, c]^T p = p_c for an identity state
+    T hs = (in ? pt : hab) - gxs;   // AB[:, c]^T p = p_c for an identity state
+    if constexpr (SX) {   // an active row (k, s), 1 <= k: the penalty on G[s, s], nu_k[s] in h_s
+      const T rs = (k > 0 && cu.fs != 0) ? T(SX17_RHO) : T(0);
+#pragma unroll
+      for (int i = 0; i < NX17; ++i) Gs[i] += (i == s) ? rs : T(0);
+      hs += cu.nus;   // (nu_0 stays 0)
+    }
     T spc_own = T(0);
 #pragma unroll
     for (int r5 = 0; r5 < 5; ++r5) spc_own += cu.a8[r5] * Pc[c8row(r5)];   // (P a)_s
@@ -1650,6 +1690,10 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
       h8 = cu.a8[0] * pt8 + cu.a8[1] * bcast<tstate(2)>(pt) + cu.a8[2] * bcast<tstate(14)>(pt) +
            cu.a8[3] * bcast<tstate(15)>(pt) + cu.a8[4] * bcast<tstate(16)>(pt) - gx8;
       G88 += sQ[OM * NX17 + xpos(OM)];
+      if constexpr (SX) {
+        G88 += (k > 0 && cu.f8 != 0) ? T(SX17_RHO) : T(0);
+        h8 += cu.nu8;
+      }
     }
     // ---- Huu masked (oracle.ocp._masked_stage, delta = 0): row and column of a clamped input
     // zeroed, diagonal 1, its rows of H_ux and h_u zeroed; Cholesky, k, K columns
@@ -1729,8 +1773,10 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
     a.gx0[b * NX17 + s] = bad ? qnan : -pj;
     if (t == 0) a.gx0[b * NX17 + OM] = bad ? qnan : -p8;
   }
-  if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : (qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL);
-  if (!a.gxref && !a.guref && !wg) return;
+  if constexpr (!SX) {
+    if (valid && t == 0) a.status[b] = bad ? MPCB_STATUS_NAN : (qp_ok ? MPCB_STATUS_OK : MPCB_STATUS_QP_FAIL);
+    if (!a.gxref && !a.guref && !wg) return;
+  }
   __syncthreads();   // K and k are read back across lanes
 
   // ---- forward from dx_0 = 0 over the stored gains and the cached [A|B] (forward<>'s ring of
@@ -1810,6 +1856,43 @@ __device__ __forceinline__ void vjp17_body(const Vjp17Args<T>& a, const Pw17<T>&
     oxs[(int64_t)N * NX17 + s] = bad ? qnan : ox;
     oxs[(int64_t)N * NX17 + OM] = bad ? qnan : ox8;
   }
+  if constexpr (!SX) {
+    return;
+  } else {
+    __syncthreads();   // dx is read back across lanes (state 8's entries)
+    T eq = T(0), dm = T(0);
+    for (int k = 0; k <= N; ++k) {
+      const T vs = fabs(w.DX[(int64_t)k * NX17 + s]), v8 = fabs(w.DX[(int64_t)k * NX17 + OM]);
+      const bool on = k > 0 && k < N;
+      const bool as = on && fsp[(int64_t)k * NX17 + s] != 0, a8 = on && fsp[(int64_t)k * NX17 + OM] != 0;
+      dm = fmax(dm, fmax(vs, v8));
+      eq = fmax(eq, fmax(as ? vs : T(0), a8 ? v8 : T(0)));
+    }
+    eq = row_max(eq);
+    dm = row_max(dm);
+    // (a NaN or indefinite instance has nothing to converge to: its status says so)
+    done = done || bad || !qp_ok || eq <= T(SX17_EQ) * fmax(T(1), dm);
+    const bool last = pass + 1 >= SX17_ITERS || __builtin_amdgcn_ballot_w64(!done) == 0;
+    if (last) {
+      if (valid && t == 0)
+        a.status[b] = bad ? MPCB_STATUS_NAN
+                          : (!qp_ok ? MPCB_STATUS_QP_FAIL : (done ? MPCB_STATUS_OK : MPCB_STATUS_MAXITER));
+      return;
+    }
+    // nu_k[i] += rho dx_k[i] on the active rows; a finished group stores what it loaded
+    for (int k = 1; k < N; ++k) {
+      T* const ns = w.NU + (int64_t)k * NX17 + s;
+      T* const n8 = w.NU + (int64_t)k * NX17 + OM;
+      const T os = *ns, o8 = *n8;
+      const T us = os + T(SX17_RHO) * w.DX[(int64_t)k * NX17 + s];
+      const T u8 = o8 + T(SX17_RHO) * w.DX[(int64_t)k * NX17 + OM];
+      const bool as = !done && fsp[(int64_t)k * NX17 + s] != 0, a8 = !done && fsp[(int64_t)k * NX17 + OM] != 0;
+      *ns = as ? us : os;
+      *n8 = a8 ? u8 : o8;
+    }
+    __syncthreads();   // nu is read back across lanes by the next pass
+  }
+  }   // pass
 }
 
 template <class T>
@@ -1820,6 +1903,16 @@ __global__ void __launch_bounds__(64) vjp17_kernel(Vjp17Args<T> a) {
 template <class T>
 __global__ void __launch_bounds__(64) vjp17_pw_kernel(Vjp17Args<T> a, Pw17<T> pw) {
   vjp17_body<T, true>(a, pw);
+}
+
+// the product with active state rows (mpcb_solve_vjp17_sx): the handle's weights, an instance's own
+__global__ void __launch_bounds__(64) vjp17_sx_kernel(Vjp17Args<double> a, const uint8_t* fixed_x) {
+  vjp17_body<double, false, true>(a, Pw17<double>{}, fixed_x);
+}
+
+__global__ void __launch_bounds__(64) vjp17_sx_pw_kernel(Vjp17Args<double> a, Pw17<double> pw,
+                                                         const uint8_t* fixed_x) {
+  vjp17_body<double, true, true>(a, pw, fixed_x);
 }
 
 // The weight gradients of one instance per workgroup, from the adjoint trajectory the forward
@@ -2152,6 +2245,18 @@ template <class T> hipError_t launch_vjp17_pw(const Vjp17Args<T>& a, const Pw17<
 }
 template hipError_t launch_vjp17_pw<double>(const Vjp17Args<double>&, const Pw17<double>&, hipStream_t);
 template hipError_t launch_vjp17_pw<float>(const Vjp17Args<float>&, const Pw17<float>&, hipStream_t);
+
+hipError_t launch_vjp17_sx(const Vjp17Args<double>& a, const Pw17<double>* pw, const uint8_t* fixed_x,
+                           hipStream_t st) {
+  using T = double;
+  const dim3 grid((unsigned)((a.nb + q17::GR - 1) / q17::GR));
+  hipLaunchKernelGGL((q17::vjp17_lin_kernel<T>), dim3((unsigned)((a.nb * a.N + GQ17 - 1) / GQ17)), dim3(64), 0, st, a);
+  if (pw) hipLaunchKernelGGL(q17::vjp17_sx_pw_kernel, grid, dim3(64), 0, st, a, *pw, fixed_x);
+  else hipLaunchKernelGGL(q17::vjp17_sx_kernel, grid, dim3(64), 0, st, a, fixed_x);
+  if (a.gQ || a.gR || a.gQN)
+    hipLaunchKernelGGL((q17::vjp17_w_kernel<T>), dim3((unsigned)a.nb), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
 
 template <class T> hipError_t launch_gains17(const Gains17Args<T>& a, hipStream_t st) {
   const Vjp17Args<T>& v = a.v;

@@ -21,7 +21,15 @@ to the plain product on the same build.
 tools/bench_full17.py), with an empty and a half-full mask and, with ``--weights``, all six
 outputs, next to the unboxed mpcb_solve_iterate of the same handle.
 
+``--full17 --state-rows`` times mpcb_solve_vjp17_sx on the 17/6 state-box bench draws (the draws of
+tools/bench_full17.py --bounds all, 4096 x N = 60, fp64) with the two masks of a real solve_iterate
+step, next to the same call without state rows (fixed_x = NULL: the kernels of mpcb_solve_vjp17)
+and the state-box solve itself.  The device does not report its pass counts, so they come from the
+NumPy model of the recursion (tests/vjp17x_ref.py ``al_x``) on the first ``--model`` instances,
+whose statuses are compared with the device's.
+
     python tools/bench_vjp.py [--runs 20] [--warmup 5] [--inner 5] [--shapes c2,c3,c4] [--weights] [--full17]
+                              [--state-rows [--model 64]]
 """
 import argparse
 import json
@@ -211,6 +219,85 @@ def bench_full17(runs, warmup, inner, weights=False, B=4096, N=60, dtype='f64'):
     return out
 
 
+def bench_full17_sx(runs, warmup, inner, model=64, B=4096, N=60):
+    """mpcb_solve_vjp17_sx with the masks of a real state-box solve (module docstring)."""
+    import numpy as np
+    import torch
+
+    from mpc_blaster_amd import BatchedMPC, MPCConfig, _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(root, 'tools'), os.path.join(root, 'tests')]
+    from sbox_stall_study import draws   # the 17/6 bench draws (tools/bench_full17.py --bounds all)
+    x0, xref, uref, p, lbu, ubu, lbx, ubx = draws(N, B)
+    m = BatchedMPC(MPCConfig.full(N=N, lbu=lbu, ubu=ubu, lbx=lbx, ubx=ubx), max_batch=B)
+    dt, dev = m.dtype, m._tdev
+    x0d, xr, ur, pt = (torch.as_tensor(a, dtype=dt, device=dev) for a in (x0, xref, uref, p))
+    m.set_params(pt)
+    m.solve(x0d, xr, ur)   # the iterate: one rollout-mode step
+    xbar, ubar = m.get_state_trajectory().clone(), m.get_input_trajectory().clone()
+    m.solve_iterate(x0d, xbar, ubar, xr, ur)
+    X, U, sst = m.get_state_trajectory().clone(), m.get_input_trajectory().clone(), m.get_status().clone()
+    fixed, fixed_x = m.active_mask17(U), m.active_mask17x(X)
+    gen = torch.Generator(device=dev).manual_seed(1017)
+    gX = torch.randn((B, N + 1, 17), dtype=dt, device=dev, generator=gen)
+    gU = torch.randn((B, N, 6), dtype=dt, device=dev, generator=gen)
+    u0o, Xo, Uo = torch.empty((B, 6), dtype=dt, device=dev), torch.empty_like(X), torch.empty_like(U)
+    gx0, gxr, gur = torch.empty((B, 17), dtype=dt, device=dev), torch.empty_like(xbar), torch.empty_like(ubar)
+    sts = {k: torch.empty((B,), dtype=torch.int32, device=dev) for k in ('solve_iterate', 'vjp17', 'vjp17_sx')}
+    P, null, st = m._ptr, m._ptr(None), m._stream()
+
+    def sx_call(key, fxx):
+        return lambda: _lib.check(m.lib.mpcb_solve_vjp17_sx(
+            m._h, B, P(xbar), P(ubar), P(fixed), fxx, null, null, null, 0, null, 0, null, 0, null, 0, null, 0,
+            P(gX), P(gU), P(gx0), P(gxr), P(gur), null, null, null, P(sts[key]), st))
+    variants = {
+        'solve_iterate': lambda: _lib.check(m.lib.mpcb_solve_iterate(
+            m._h, B, P(x0d), 17, P(xbar), P(ubar), P(xr), 0, P(ur), 0, null, 0, P(u0o), P(Xo), P(Uo),
+            P(sts['solve_iterate']), st)),
+        'vjp17': sx_call('vjp17', null),
+        'vjp17_sx': sx_call('vjp17_sx', P(fixed_x)),
+    }
+    for _ in range(warmup):
+        for f in variants.values():
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(runs):
+        for k, f in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _i in range(inner):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) / inner)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    solved = (sst == 0).cpu().numpy()
+    rows = fixed_x.sum(dim=(1, 2)).cpu().numpy()
+    dst = sts['vjp17_sx'].cpu().numpy()
+    out = dict(shape='full17_state_rows', B=B, N=N, dtype='f64', runs=runs, inner=inner,
+               **{f'{k}_ms': round(v, 4) for k, v in med.items()},
+               **{f'{k}_min_ms': round(min(v), 4) for k, v in t.items()},
+               sx_over_vjp17=round(med['vjp17_sx'] / med['vjp17'], 3),
+               sx_over_solve=round(med['vjp17_sx'] / med['solve_iterate'], 3),
+               solve_status_ok=int(solved.sum()),
+               rows_per_instance=[int(rows[solved].min()), float(np.median(rows[solved])), int(rows[solved].max())],
+               sx_status_counts_of_solved={str(k): int(((dst == k) & solved).sum()) for k in np.unique(dst[solved])})
+    if model > 0:   # the pass counts of the recursion's NumPy model on the first instances
+        import vjp17x_ref as xr
+        from oracle.full import FullSpec
+        n = min(model, B)
+        f = lambda a: a[:n].cpu().numpy()   # noqa: E731
+        al = xr.al_x(f(xbar), f(ubar), p[:n], f(fixed), f(fixed_x), f(gX), f(gU),
+                     FullSpec(N=N, lbu=lbu, ubu=ubu, lbx=lbx, ubx=ubx))
+        ok = solved[:n]
+        out.update(model_instances=int(ok.sum()),
+                   model_passes_hist=np.bincount(al['passes'][ok], minlength=xr.SX17_ITERS + 1).tolist(),
+                   model_status_equal=int((al['status'][ok] == dst[:n][ok]).sum()))
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--runs', type=int, default=20)
@@ -221,7 +308,16 @@ def main():
                     help='also time mpcb_solve_vjp_w (the weight gradients gQ, gR, gQN in the same launch)')
     ap.add_argument('--full17', action='store_true',
                     help='time mpcb_solve_vjp17 (17/6 model, 4096 x N = 60, fp64) instead of the 12/4 shapes')
+    ap.add_argument('--state-rows', action='store_true',
+                    help='with --full17: time mpcb_solve_vjp17_sx on the state-box bench draws')
+    ap.add_argument('--model', type=int, default=64,
+                    help='with --state-rows: instances whose pass counts the NumPy model reports (0: none)')
     a = ap.parse_args()
+    if a.state_rows:
+        if not a.full17:
+            ap.error('--state-rows belongs to --full17')
+        bench_full17_sx(a.runs, a.warmup, a.inner, a.model)
+        return
     if a.full17:
         bench_full17(a.runs, a.warmup, a.inner, a.weights)
         return
