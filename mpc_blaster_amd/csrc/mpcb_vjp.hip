@@ -461,28 +461,22 @@ __global__ void __launch_bounds__(64) vjp_kernel(VjpArgs<T> a) {
 
 int64_t vjp_slot_elems(int N) { return (int64_t)N * (GROUPS * LIN_STAGE + 64 * VJP_KR); }
 
-template <class T> hipError_t launch_vjp(const VjpArgs<T>& a, int grid, hipStream_t st) {
+template <class T, int PW> static hipError_t launch_vjp_pw(const VjpArgs<T>& a, int grid, hipStream_t st) {
   const bool wg = a.gQ || a.gR || a.gQN;   // no weight gradient asked for: the plain kernels
-  if (a.Qw) {   // per-instance weights (mpcb_solve_vjp_pw): all three pointers are set
-    if (a.box && wg)
-      hipLaunchKernelGGL((vjp_kernel<T, 1, 1, 1>), dim3(grid), dim3(64), 0, st, a);
-    else if (wg)
-      hipLaunchKernelGGL((vjp_kernel<T, 0, 1, 1>), dim3(grid), dim3(64), 0, st, a);
-    else if (a.box)
-      hipLaunchKernelGGL((vjp_kernel<T, 1, 0, 1>), dim3(grid), dim3(64), 0, st, a);
-    else
-      hipLaunchKernelGGL((vjp_kernel<T, 0, 0, 1>), dim3(grid), dim3(64), 0, st, a);
-    return hipGetLastError();
-  }
   if (a.box && wg)
-    hipLaunchKernelGGL((vjp_kernel<T, 1, 1>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((vjp_kernel<T, 1, 1, PW>), dim3(grid), dim3(64), 0, st, a);
   else if (wg)
-    hipLaunchKernelGGL((vjp_kernel<T, 0, 1>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((vjp_kernel<T, 0, 1, PW>), dim3(grid), dim3(64), 0, st, a);
   else if (a.box)
-    hipLaunchKernelGGL((vjp_kernel<T, 1, 0>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((vjp_kernel<T, 1, 0, PW>), dim3(grid), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((vjp_kernel<T, 0, 0>), dim3(grid), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((vjp_kernel<T, 0, 0, PW>), dim3(grid), dim3(64), 0, st, a);
   return hipGetLastError();
+}
+
+// a.Qw: per-instance weights (mpcb_solve_vjp_pw: all three pointers are set)
+template <class T> hipError_t launch_vjp(const VjpArgs<T>& a, int grid, hipStream_t st) {
+  return a.Qw ? launch_vjp_pw<T, 1>(a, grid, st) : launch_vjp_pw<T, 0>(a, grid, st);
 }
 
 template hipError_t launch_vjp<double>(const VjpArgs<double>&, int, hipStream_t);
